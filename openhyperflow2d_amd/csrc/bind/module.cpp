@@ -11,6 +11,7 @@
 
 #include "../core/case.hpp"
 #include "../core/checkpoint.hpp"
+#include "../core/lean_euler.hpp"
 #include "../core/postproc.hpp"
 #include "../core/solver.hpp"
 #include "../hip/chem_mech.hpp"
@@ -533,6 +534,23 @@ PYBIND11_MODULE(_hf2d, m) {
         if (!py_.empty()) save_y_heat_flux(py_, c, c.J);
       });
 
+  m.def(
+      "lean_tile_geom",
+      [](int ncols, int ny, int block, int tj, int cpt) {
+        const LeanTile T = lean_tile_geom(ncols, ny, block, tj, cpt);
+        py::dict d;
+        d["TI"] = T.TI;
+        d["TJ"] = T.TJ;
+        d["W"] = T.W;
+        d["NC"] = T.NC;
+        d["nbi"] = T.nbi;
+        d["nbj"] = T.nbj;
+        d["TIh"] = T.TIh;
+        d["CPT"] = T.CPT;
+        return d;
+      },
+      py::arg("ncols"), py::arg("ny"), py::arg("block"), py::arg("tj") = 0, py::arg("cpt") = 1,
+      "lean tile geometry (lean_euler.hpp LeanTile) of a strip of ncols x ny cells");
   m.def("sk_eligible", [](const Case& c) { std::string w; const int md = sk_eligible(c, &w); return py::make_tuple(md, w); },
         py::arg("case"), "split-kernel specialisation (0 generic, 1 single-gas laminar, 2 single-gas turbulent; reason)");
   m.def("smooth", [](py::array_t<double, py::array::c_style> a, int axis) {
@@ -867,8 +885,29 @@ PYBIND11_MODULE(_hf2d, m) {
       .def_readonly("chem_kernel_used", &DeviceSolver::chem_kernel_used)
       .def_readonly("chem_fast_ok", &DeviceSolver::chem_fast_ok)
       .def_readonly("graph_launches", &DeviceSolver::graph_launches)
+      .def_readonly("graph_captures", &DeviceSolver::graph_captures)
       .def_readwrite("lean_cpt", &DeviceSolver::lean_cpt)
       .def_readwrite("lean_nt", &DeviceSolver::lean_nt)
+      .def_readwrite("cu_count", &DeviceSolver::cu_count)
+      .def_property_readonly("lean_tile_last",
+                             [](const DeviceSolver& s) {
+                               const DeviceSolver::TileLast& t = s.lean_tile_last;
+                               py::dict d;
+                               d["nt"] = t.nt;
+                               d["cpt"] = t.cpt;
+                               d["TI"] = t.TI;
+                               d["TJ"] = t.TJ;
+                               d["nbi"] = t.nbi;
+                               d["nbj"] = t.nbj;
+                               d["stagger"] = t.stagger;
+                               d["fx"] = t.fx;
+                               d["var"] = t.var;
+                               d["seen"] = t.seen;
+                               d["dt_read"] = t.dt_read;
+                               return d;
+                             },
+                             "geometry and variant (0 plain, 1 outputs, 2 residual) of the last lean tile launch; "
+                             "nt == 0 after a step on any other kernel")
       .def_readwrite("sgl", &DeviceSolver::sgl)
       .def_readonly("sgl_ok", &DeviceSolver::sgl_ok)
       .def_readonly("sgl_why", &DeviceSolver::sgl_why)

@@ -3840,6 +3840,7 @@ struct DeviceSolver::GraphCache {
   // replay), and the window ends with its last step's halo pending
   bool lns_pro = false, lns_end = false;
   ColList lns_end_list{};
+  DeviceSolver::TileLast tile_last;   // lean_tile_last of the window's last step
   ~GraphCache() {
     if (exec) (void)hipGraphExecDestroy(exec);
   }
@@ -3860,7 +3861,10 @@ uint64_t DeviceSolver::mode_signature() const {
   // the previous level's buffers from the first replayed window on)
   const int fields[] = {lean_state, (int)lean, (int)fused, (int)lean_tile, (int)(lean_sg && lean_sg_ok), lean_cpt,
                         lean_tj, lean_nt, lean_wgcu, (int)(p2p_fuse && impl->p2p.on), (int)(sgl && sgl_ok), lns_state,
-                        (int)lean_ns, (int)lean_mech, sbuf, abuf, dsbuf, pbuf, cbuf};
+                        (int)lean_ns, (int)lean_mech, sbuf, abuf, dsbuf, pbuf, cbuf,
+                        // (settings a captured launch bakes in: the cpt gate and the stagger rounds,
+                        // the mailbox push kernel, the dt read, the skipped stores, the ghost prologue)
+                        cu_count, push_per, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue};
   uint64_t h = 0;
   for (int f : fields) h = h * 1000003ull + (uint64_t)(f + 1);
   return h;
@@ -3908,6 +3912,11 @@ void DeviceSolver::run_graph() {
       lns_ghost_pending = lns_last_valid = true;
     }
     dt_word_valid = false;   // (conservative: the next eager step reads the shards too)
+    {
+      const TileLast prev = lean_tile_last;
+      lean_tile_last = graph->tile_last;
+      if (prev.nt == lean_tile_last.nt && prev.cpt == lean_tile_last.cpt) lean_tile_last.seen |= prev.seen;
+    }
     nstep += GRAPH_STEPS;   // ping-pong parities are unchanged after an even number of steps
     pending.clear();
     graph_launches++;
@@ -3966,6 +3975,8 @@ void DeviceSolver::run_graph() {
   graph->lns_pro = first_pro;
   graph->lns_end = lns_ghost_pending && lns_last_valid;
   graph->lns_end_list = m.lns_pend;
+  graph->tile_last = lean_tile_last;
+  graph_captures++;
   HIP_CHECK(hipGraphLaunch(graph->exec, m.stream));
   nstep += GRAPH_STEPS;
   graph_launches++;
@@ -4328,6 +4339,8 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   // layout or nothing)
   lns_prev_valid = lns_last_valid;
   lns_last_valid = false;
+  const TileLast tile_prev = lean_tile_last;
+  lean_tile_last = TileLast{};
   const bool tile_path = euler && lean && lean_ok && lean_tile &&
                          lean_state == 1 && P.ny >= LEAN_TILE_MIN_TJ;
   // (a fused lean N-S step unpacks the previous fused step's halo itself)
@@ -4370,6 +4383,16 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     // MIN follows in the next fused step's first workgroup or in
     // hf2d_p2p_complete before any other consumer (fx_pending)
     X.defer = fx_step && P.lag_dt ? 1 : 0;
+    lean_tile_last.nt = nt;
+    lean_tile_last.cpt = cpt;
+    lean_tile_last.TI = T.TI;
+    lean_tile_last.TJ = T.TJ;
+    lean_tile_last.nbi = T.nbi;
+    lean_tile_last.nbj = T.nbj;
+    // (the stagger block is compiled into the single-gas two-cell 256-thread plain kernel only)
+    lean_tile_last.stagger = HF2D_TILE_STAGGER && sg && cpt == 2 && !fx_step && nt == BLOCK ? P.stagger : 0;
+    lean_tile_last.fx = fx_step ? 1 : 0;
+    lean_tile_last.seen = tile_prev.nt == nt && tile_prev.cpt == cpt ? tile_prev.seen : 0;
     // RCCL / in-process transports: edge tiles first, their halo on the comm
     // stream while the interior tiles compute, then the dt MIN
     // (the decision must be the same on every rank -- the exchange sequence
@@ -4377,6 +4400,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     const bool split = comm_overlap && !fx_step && !m.p2p.on && (m.comm || m.local) && m.nranks > 1 &&
                        !want_res && !out && !tile_trace && lean_occ == 0;
     if (split) {
+      lean_tile_last.seen |= 1;   // (the part launches are plain steps)
       if (!m.comm_stream) {
         HIP_CHECK(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreateWithFlags(&m.ev_edge, hipEventDisableTiming));
@@ -4422,6 +4446,8 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     // variant: 0 plain, 1 outputs, 2 residual (all variants of one step use
     // the cpt the tile geometry was built for)
     const int var = want_res ? 2 : out ? 1 : 0;
+    lean_tile_last.var = var;
+    lean_tile_last.seen |= 1 << var;
     if (tile_trace && var == 0 && !fx_step)
       hipLaunchKernelGGL(nt == BLOCK ? kTileTr[sg][cpt - 1] : kTileTrNt[nts][cpt - 1], dim3(ntile), dim3(nt), shmem,
                          st, P, L, T, m.sc, slot, slot_next, serial, m.partials, tile_trace);
@@ -4431,6 +4457,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
       // fold is deferred, lagged dt)
       const bool word = dt_read_mode >= 1 && !X.defer;
       if (word && dt_word_ok) P.dt_read = 2;
+      lean_tile_last.dt_read = P.dt_read;
       hipLaunchKernelGGL(nt == BLOCK ? kTileFx[sg][cpt - 1][var] : kTileFxNt[nts][cpt - 1][var], dim3(ntile),
                          dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials, fx_device(X));
       dt_word_valid = word;
@@ -4456,6 +4483,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
         P.dt_fold = 1;
         P.host_done = m.host_done;
       }
+      lean_tile_last.dt_read = P.dt_read;
       if (nt != BLOCK)
         hipLaunchKernelGGL(kTileNt[nts][cpt - 1][var], dim3(ntile), dim3(nt), shmem, st, P, L, T, m.sc, slot,
                            slot_next, serial, m.partials, 0);

@@ -201,6 +201,18 @@ class DeviceSolver : public SolverBase {
   int lean_cpt = 2;        // cells per thread in the tiled kernel: 1 or 2 (2: measured ~20% faster)
   int lean_nt = 256;       // threads per tile workgroup: 256, or 128 / 64 (single gas; small strips)
   int cu_count = 256;
+  // geometry and variant of the last lean tile launch do_step issued (a step
+  // on any other kernel clears it: nt == 0); stagger: the start delay the
+  // launched kernel applies (0 where it is compiled out), var: 0 plain,
+  // 1 outputs, 2 residual; seen: bit v set for every variant v launched in
+  // the unbroken run of tile steps with this nt and cpt that the last one
+  // ends (the last step of a host call is never a plain one); dt_read: how
+  // it read the step's dt (StepParams::dt_read).  Tests assert through it
+  // which variant ran.
+  struct TileLast {
+    int nt = 0, cpt = 0, TI = 0, TJ = 0, nbi = 0, nbj = 0, stagger = 0, fx = 0, var = 0, seen = 0, dt_read = 0;
+  };
+  TileLast lean_tile_last;
   bool lean_sg_ok = false;
   bool lean_has_cauchy_x = true;   // some node reads dS/dx of an x neighbour (halo must carry it)
   void set_lean_plain(bool on);
@@ -271,6 +283,7 @@ class DeviceSolver : public SolverBase {
   // step graphs (see device_solver.hip)
   bool use_graph = true;
   long graph_launches = 0;
+  long graph_captures = 0;   // windows captured (a replay needs the same mode_signature)
   void flush_pending();
 
  private:

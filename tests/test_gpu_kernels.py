@@ -105,11 +105,15 @@ def test_small_workgroup_tiles_bitwise(gpu, nt, cpt, tj):
     ref = gpu.Simulation(text, "gpu")
     s = gpu.Simulation(text, "gpu")
     ref.solver.lean_nt, ref.solver.lean_cpt, ref.solver.lean_tj = 256, 2, 0
+    # (104 two-cell tiles: fewer than two per CU of the device, and do_step would run one cell per thread)
+    ref.solver.cu_count = 32
     s.solver.lean_nt, s.solver.lean_cpt, s.solver.lean_tj = nt, cpt, tj
     for n, res in [(5, True), (30, False), (7, True)]:
         s.step(n, residual=res)
         ref.step(n, residual=res)
         assert s.summary()["dt"] == ref.summary()["dt"]
+        assert (ref.solver.lean_tile_last["nt"], ref.solver.lean_tile_last["cpt"]) == (256, 2)
+        assert (s.solver.lean_tile_last["nt"], s.solver.lean_tile_last["cpt"]) == (nt, cpt)
     assert s.summary()["time"] == ref.summary()["time"]
     np.testing.assert_allclose(s.summary()["rms"], ref.summary()["rms"], rtol=1e-12, atol=0)
     for f in FIELDS + ["k", "R", "CP"]:
@@ -166,17 +170,21 @@ def test_lean_bitwise_with_switches(gpu):
 
 
 def _virtual_ranks(hf, text, nranks, schedule, lean=True, p2p=False, fuse=True, toggle=False, corrupt=False,
-                   stats=None, setup=None, chunk_hook=None, fields=FIELDS, parts=None):
+                   stats=None, setup=None, chunk_hook=None, fields=FIELDS, parts=None, case_hook=None):
     """Run the strip decomposition as `nranks` DeviceSolvers on ONE GPU, one
     host thread each, halos through the in-process LocalGroup transport (or,
     p2p=True, the device-side mailbox transport: one exchange kernel per step,
-    step graphs on)."""
+    step graphs on).  case_hook(case): applied to every rank's whole-grid Case
+    before its solver uploads it (a perturbed start)."""
     import threading
 
     from openhyperflow2d_amd.parallel.strips import balanced_columns
 
     nat = hf.native()
     cases = [nat.Case.from_deck(text, ".", False) for _ in range(nranks)]
+    if case_hook is not None:
+        for c in cases:
+            case_hook(c)
     parts = parts or balanced_columns(np.asarray(cases[0].field("solid")), nranks)
     group = nat.LocalGroup(nranks)
     solvers = []
@@ -433,8 +441,9 @@ def test_lean_ns_strips_match_single_gpu(gpu, deck, nranks, p2p):
     assert min(lean_steps) > 0, stats
     if fx:
         assert min(stats["p2p_mwg_exchanges" if deck == "scramjet" else "lns_fx_steps"]) > 0, stats
-        if deck != "scramjet":   # the next fused step unpacked the halo in its edge tiles
-            assert min(stats["lns_prologue_steps"]) > 0, stats
+        # the next fused step unpacked the halo in its edge tiles (mechanism:
+        # the halo the push kernel left in the mailbox after the state kernel)
+        assert min(stats["lns_prologue_steps"]) > 0, stats
     if not p2p:   # in-process transport: edge tiles first, halo overlapped (mechanism: + their kinetics)
         assert min(stats["overlap_steps"]) > 0, stats
     ref = gpu.Simulation(text, "gpu")
@@ -905,9 +914,16 @@ def test_tile_stagger_is_timing_only(gpu, monkeypatch, stagger):
     s = gpu.Simulation(text, "gpu")
     assert s.solver.tile_stagger == stagger
     s.solver.lean_cpt = ref.solver.lean_cpt = 2
+    # 95 two-cell tiles: at least two per CU (else do_step runs one cell per
+    # thread, whose kernel has no stagger block) and at most four rounds
+    s.solver.cu_count = ref.solver.cu_count = 32
     for n, res in [(5, True), (25, False), (3, True)]:
         s.step(n, residual=res)
         ref.step(n, residual=res)
+        last = s.solver.lean_tile_last
+        assert (last["nt"], last["cpt"], last["stagger"]) == (256, 2, stagger), last
+        assert last["seen"] & 1, last   # plain steps, the variant that staggers in production
+        assert ref.solver.lean_tile_last["cpt"] == 2 and ref.solver.lean_tile_last["stagger"] == 0
     assert s.summary()["dt"] == ref.summary()["dt"]
     for f in FIELDS:
         np.testing.assert_array_equal(s.field(f), ref.field(f), err_msg=f)

@@ -56,6 +56,47 @@ def test_lean_equals_generic(hf, name, tile, sg, cpt, tj, nt):
     np.testing.assert_array_equal(_records_wo_scratch(a), _records_wo_scratch(b))
 
 
+def _sweep():
+    import openhyperflow2d_amd as pkg
+
+    from tests.perturb import shape_sweep
+
+    return shape_sweep(pkg.native())
+
+
+@pytest.mark.parametrize("nt,cpt,tj,nx,ny,top", _sweep())
+def test_tile_emulation_shape_sweep(hf, nt, cpt, tj, nx, ny, top):
+    """The host tile emulation (unstaged LDS slots poisoned with NaN) at the
+    edges of the tiling -- strips narrower than a tile, one tile + one column,
+    one-cell-high last tile rows, a live last grid row, TI = 1, idle threads
+    -- from a start in which every cell differs from its neighbours
+    (tests/perturb.py), so a wrong neighbour or ghost read shows: == the
+    generic per-cell stepper."""
+    from tests.perturb import FIELDS as F8
+    from tests.perturb import SCHEDULE, flat_fraction, perturb, sweep_deck
+
+    text = sweep_deck(nx, ny, top)
+    a = hf.Simulation(text, "cpu", lean=False)
+    b = hf.Simulation(text, "cpu", lean=True)
+    perturb(a, 1)
+    perturb(b, 1)
+    b.solver.lean_tile, b.solver.lean_sg = True, True
+    b.solver.lean_nt, b.solver.lean_cpt, b.solver.lean_tj = nt, cpt, tj
+    assert b.solver.lean_ok and b.solver.lean_sg_ok, b.solver.lean_why
+    assert flat_fraction(a) == 0.0
+    for n, res in SCHEDULE:
+        a.step(n, residual=res)
+        b.step(n, residual=res)
+        sa, sb = a.summary(), b.summary()
+        assert sa["dt"] == sb["dt"] and sa["time"] == sb["time"]
+        if res:
+            np.testing.assert_allclose(sa["rms"], sb["rms"], rtol=1e-12, atol=0)
+        for f in F8:
+            np.testing.assert_array_equal(a.field(f), b.field(f), err_msg=f)
+    assert np.isfinite(a.field("rho")).all() and flat_fraction(a) <= 0.02
+    np.testing.assert_array_equal(_records_wo_scratch(a), _records_wo_scratch(b))
+
+
 def test_lean_generic_switching(hf):
     text = _decks()["wedge15"]
     a = hf.Simulation(text, "cpu", lean=False)
