@@ -5,6 +5,7 @@
                                      [--no-checkpoint] [--no-lean] [--metrics FILE]
                                      [--profile FILE] [--fault-inject step:N,rank:R,kind:nan|kill]
                                      [--transport p2p|rccl]
+                                     [--probe-history FILE.npz [--probe-capacity N]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
   python -m openhyperflow2d_amd info deck.dat
   python -m openhyperflow2d_amd build
@@ -38,6 +39,11 @@ def _cmd_run(a) -> int:
     os.makedirs(outdir, exist_ok=True)
     nat = hf.native()
     backend = a.backend or ("gpu" if hf.gpu_available() else "cpu")
+    if a.probe_history and world > 1:
+        if rank == 0:
+            print("--probe-history records in one process only; this is a %d-rank launch "
+                  "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
+        return 2
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -62,6 +68,15 @@ def _cmd_run(a) -> int:
     if rank == 0:
         print("hf2d: %s  %dx%d  backend=%s  ranks=%d" % (os.path.basename(a.deck), sim.case.nx, sim.case.ny,
                                                           backend, world), flush=True)
+    probe_cells = []
+    if a.probe_history:
+        # the deck's monitor points, every step (Monitors-<P>.plt keeps its NOutStep cadence)
+        probe_cells = sim.monitor_cells()
+        try:
+            sim.record_probes(probe_cells, a.probe_capacity)
+        except (ValueError, RuntimeError) as e:
+            print("--probe-history: %s" % e, file=sys.stderr, flush=True)
+            return 2
     try:
         cycles, log = sim.run(max_cycles=a.cycles, outdir=outdir, outputs=True, checkpoint=not a.no_checkpoint,
                               verbose=True, metrics=a.metrics or "", profile=a.profile or "",
@@ -69,6 +84,17 @@ def _cmd_run(a) -> int:
     except RuntimeError as e:
         print(str(e), file=sys.stderr, flush=True)
         return 3
+    if a.probe_history:
+        import numpy as np
+
+        from .models.simulation import PROBE_VARS
+
+        h = sim.probe_history()
+        with open(a.probe_history, "wb") as f:   # (np.savez on a path would append ".npz")
+            np.savez(f, times=h["times"], values=h["values"], cells=np.asarray(probe_cells, dtype=np.int64),
+                     vars=np.asarray(PROBE_VARS), total=np.int64(h["total"]))
+        print("probe history: %d of %d steps x %d points -> %s" % (h["values"].shape[0], h["total"], len(probe_cells),
+                                                                    a.probe_history), flush=True)
     if rank == 0:
         sys.stdout.write(log)
         print("\nReady. Computation finished (%d cycles)." % cycles, flush=True)
@@ -158,6 +184,11 @@ def main(argv=None) -> int:
     r.add_argument("--fault-inject", dest="fault_inject", metavar="SPEC",
                    help="step:N[,rank:R][,kind:nan|kill] -- test hook for the failure/restart paths")
     r.add_argument("--transport", choices=["p2p", "rccl"], help="multi-GPU exchange (default p2p)")
+    r.add_argument("--probe-history", dest="probe_history", metavar="FILE.npz",
+                   help="record p, T, rho, U, V at the deck's monitor points after every step (one process only) "
+                        "and write times / values / cells / vars to this file")
+    r.add_argument("--probe-capacity", dest="probe_capacity", type=int, default=4096, metavar="N",
+                   help="rows the recorder keeps: the last N steps (default 4096)")
     d = sub.add_parser("deck", help="write a generated deck")
     d.add_argument("name")
     d.add_argument("--nx", type=int)

@@ -303,6 +303,13 @@ PYBIND11_MODULE(_hf2d, m) {
       .def_property_readonly("project", [](const Case& c) { return c.cfg.project; })
       .def_property_readonly("global_time", [](const Case& c) { return c.global_time; })
       .def_property_readonly("wall_nodes", [](const Case& c) { return c.wall_nodes; })
+      .def_property_readonly("monitor_cells",
+                             [](const Case& c) {   // the cells sample_monitors reads (K8)
+                               std::vector<std::pair<int, int>> v;
+                               for (const MonitorPoint& m : c.cfg.monitors)
+                                 v.emplace_back((int)(m.x / c.cfg.dx), (int)(m.y / c.cfg.dy));
+                               return v;
+                             })
       .def("set_min_distance_to_wall", &Case::set_min_distance_to_wall, py::arg("x0") = 0.0)
       .def("set_min_distance_to_wall_bruteforce", &Case::set_min_distance_to_wall_bruteforce, py::arg("x0") = 0.0)
       .def("set_semantics", [](Case& c, const std::string& s) {
@@ -624,6 +631,37 @@ PYBIND11_MODULE(_hf2d, m) {
       .def("poison_cell", &SolverBase::poison_cell, py::arg("gi"), py::arg("j"),
            "test hook: a negative energy in cell (gi, j) (the next step reports Tg < 0)")
       .def("summary", &summary_dict)
+      .def("record_probes", &SolverBase::record_probes, py::arg("cells"), py::arg("capacity") = 4096,
+           "arm the per-step recorder on the global cells (i, j): (p, T, rho, U, V) and the time after every step")
+      .def("probe_history",
+           [](SolverBase& s) {
+             ProbeHistory H;
+             {
+               py::gil_scoped_release rel;
+               H = s.probe_history();
+             }
+             const py::ssize_t n = (py::ssize_t)H.times.size();
+             py::array_t<double> t(std::vector<py::ssize_t>{n});
+             py::array_t<double> v(std::vector<py::ssize_t>{n, (py::ssize_t)H.nprobes, (py::ssize_t)PROBE_HISTORY_VARS});
+             py::array_t<bool> o(std::vector<py::ssize_t>{(py::ssize_t)H.nprobes});
+             std::copy(H.times.begin(), H.times.end(), t.mutable_data());
+             std::copy(H.values.begin(), H.values.end(), v.mutable_data());
+             for (int q = 0; q < H.nprobes; q++) o.mutable_data()[q] = H.owned[q] != 0;
+             py::dict d;
+             d["times"] = t;
+             d["values"] = v;
+             d["total"] = H.total;
+             d["owned"] = o;
+             return d;
+           })
+      .def("clear_probe_history", &SolverBase::clear_probe_history)
+      .def("sample_monitors",
+           [](SolverBase& s) {   // the driver's output-step sampling of the deck's monitor points: [(p, T)]
+             s.sample_monitors(s.cs.cfg.monitors);
+             std::vector<std::pair<double, double>> v;
+             for (const MonitorPoint& m : s.cs.cfg.monitors) v.emplace_back(m.p, m.T);
+             return v;
+           })
       .def_readwrite("dt", &SolverBase::dt)
       .def_readonly("iter", &SolverBase::iter)
       .def_readonly("last_iter", &SolverBase::last_iter);

@@ -376,6 +376,7 @@ StepResult SolverBase::advance(bool want_res) {
   }
   cur_time_part += P.dt;
   iter++;
+  after_step();
   return r;
 }
 
@@ -424,6 +425,31 @@ void SolverBase::merge_wall_uw(const std::vector<int32_t>& slots, const std::vec
     take(sl.data(), v.data(), n);
   }
 }
+
+void SolverBase::check_probe_cells(const std::vector<std::pair<int, int>>& cells, long capacity) const {
+  if (cells.empty()) throw std::invalid_argument("record_probes: no probe cells");
+  if ((long)cells.size() > PROBE_HISTORY_MAX)
+    throw std::invalid_argument("record_probes: " + std::to_string(cells.size()) + " probes, at most " +
+                                std::to_string(PROBE_HISTORY_MAX));
+  if (capacity < 1) throw std::invalid_argument("record_probes: capacity must be at least 1");
+  const Field& J = cs.J;
+  for (const auto& c : cells) {
+    const std::string at = "(" + std::to_string(c.first) + ", " + std::to_string(c.second) + ")";
+    if (!J.in(c.first, c.second))
+      throw std::invalid_argument("record_probes: cell " + at + " is outside the " + std::to_string(J.nx) + " x " +
+                                  std::to_string(J.ny) + " grid");
+    if (!J.resident(c.first)) continue;   // trimmed strip rank: its owner checks the cell
+    const CellRecord& r = J.at(c.first, c.second);
+    if (r.is(CT_SOLID)) throw std::invalid_argument("record_probes: cell " + at + " is solid");
+    if (!r.is(CT_NODE_IS_SET)) throw std::invalid_argument("record_probes: cell " + at + " is not set");
+  }
+}
+
+void SolverBase::record_probes(const std::vector<std::pair<int, int>>&, long) {
+  throw std::runtime_error("this backend has no per-step probe recorder");
+}
+ProbeHistory SolverBase::probe_history() { throw std::runtime_error("this backend has no per-step probe recorder"); }
+void SolverBase::clear_probe_history() {}
 
 void SolverBase::sample_monitors(std::vector<MonitorPoint>& mp) {
   if (mp.empty()) return;
@@ -782,6 +808,60 @@ CpuSolver::CpuSolver(Case& c, int g0, int g1) : SolverBase(c), gi0(g0), gi1(g1 <
 void CpuSolver::poison_cell(int gi, int j) {
   const long idx = (long)(gi - gi0 + l_off) * h.ny + j;
   h.S[sbuf][(long)I_RHOE * h.N + idx] = -1.0e30;
+}
+
+void CpuSolver::record_probes(const std::vector<std::pair<int, int>>& cells, long capacity) {
+  check_probe_cells(cells, capacity);
+  probe_idx.assign(cells.size(), -1);
+  for (size_t q = 0; q < cells.size(); q++) {
+    const int i = cells[q].first;
+    if (i >= gi0 && i < gi1) probe_idx[q] = (long)(i - gi0 + l_off) * h.ny + cells[q].second;
+  }
+  probe_cap = capacity;
+  probe_total = 0;
+  probe_rows.assign((size_t)capacity * cells.size() * PROBE_HISTORY_VARS, 0.0);
+  probe_times.assign((size_t)capacity, 0.0);
+}
+
+void CpuSolver::clear_probe_history() { probe_total = 0; }
+
+// the values download() would put into the records now: the lean inviscid
+// state keeps its pressure in P2 (lean_materialize_cell copies it to p)
+void CpuSolver::after_step() {
+  if (probe_cap == 0) return;
+  const size_t np = probe_idx.size();
+  const long slot = probe_total % probe_cap;
+  const real* p = lean_state ? P2[pbuf].data() : h.p.data();
+  for (size_t q = 0; q < np; q++) {
+    real* row = &probe_rows[((size_t)slot * np + q) * PROBE_HISTORY_VARS];
+    const long c = probe_idx[q];
+    row[0] = c >= 0 ? p[c] : 0.0;
+    row[1] = c >= 0 ? h.Tg[pbuf][c] : 0.0;
+    row[2] = c >= 0 ? h.S[0][c] : 0.0;
+    row[3] = c >= 0 ? h.U[pbuf][c] : 0.0;
+    row[4] = c >= 0 ? h.V[pbuf][c] : 0.0;
+  }
+  probe_times[slot] = cs.global_time + cur_time_part;
+  probe_total++;
+}
+
+ProbeHistory CpuSolver::probe_history() {
+  if (probe_cap == 0) throw std::runtime_error("probe_history: no recorder armed (record_probes)");
+  ProbeHistory H;
+  const size_t np = probe_idx.size(), row = np * PROBE_HISTORY_VARS;
+  H.nprobes = (int)np;
+  H.total = probe_total;
+  const long n = std::min(probe_total, probe_cap), first = probe_total > probe_cap ? probe_total % probe_cap : 0;
+  H.times.resize(n);
+  H.values.resize((size_t)n * row);
+  for (long k = 0; k < n; k++) {
+    const long s = (first + k) % probe_cap;
+    H.times[k] = probe_times[s];
+    std::copy(probe_rows.begin() + s * row, probe_rows.begin() + (s + 1) * row, H.values.begin() + k * row);
+  }
+  H.owned.resize(np);
+  for (size_t q = 0; q < np; q++) H.owned[q] = probe_idx[q] >= 0 ? 1 : 0;
+  return H;
 }
 
 void RefSolver::poison_cell(int gi, int j) { cs.J.at(gi, j).S[I_RHOE] = -1.0e30; }

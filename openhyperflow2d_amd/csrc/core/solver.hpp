@@ -84,6 +84,18 @@ struct Comm {
   }
 };
 
+// Per-step probe recorder (record_probes): row k of `values` holds
+// (p, T, rho, U, V) of every probe after recorded step k, oldest first.
+constexpr int PROBE_HISTORY_VARS = 5;
+constexpr int PROBE_HISTORY_MAX = 64;
+struct ProbeHistory {
+  int nprobes = 0;
+  long total = 0;                 // steps recorded since arming (rows kept: min(total, capacity))
+  std::vector<double> times;      // [n] time after the step (summary()["time"])
+  std::vector<real> values;       // [n][nprobes][PROBE_HISTORY_VARS]
+  std::vector<uint8_t> owned;     // [nprobes] 1: this backend owns the probe's column (others read 0)
+};
+
 struct RunOptions {
   int max_cycles = -1;       // stop after this many outer cycles (-1: exit monitor only)
   bool write_outputs = true;
@@ -160,7 +172,20 @@ class SolverBase {
   // global columns [first, second) this backend owns (strip decomposition)
   virtual std::pair<int, int> owned_columns() const { return {0, cs.J.nx}; }
 
+  // Opt-in per-step probe recorder: after every step, (p, T, rho, U, V) of
+  // the global cells (i, j) and the step's time go into a ring of `capacity`
+  // rows, each value the one a download after that step yields.  Arming
+  // again replaces the recorder and restarts the count.  std::invalid_argument:
+  // no probe, more than PROBE_HISTORY_MAX, capacity < 1, a cell outside the
+  // grid, solid or unset.  Backends without a recorder refuse.
+  virtual void record_probes(const std::vector<std::pair<int, int>>& cells, long capacity);
+  virtual ProbeHistory probe_history();
+  virtual void clear_probe_history();
+  void check_probe_cells(const std::vector<std::pair<int, int>>& cells, long capacity) const;
+
  protected:
+  // called by advance() after a step the host completed (not the device's asynchronous ones)
+  virtual void after_step() {}
   bool isSrcAdd = false;
   int run_cycles(const RunOptions& opt, std::ostream* log);
   void failure_snapshot(const RunOptions& opt, const std::string& dir, const std::string& why, std::ostream* log);
@@ -196,6 +221,14 @@ class CpuSolver : public SolverBase {
   void upload() override;
   void cycle_update() override;
   void poison_cell(int gi, int j) override;
+  // host recorder: samples the stepper's own arrays after each step
+  void record_probes(const std::vector<std::pair<int, int>>& cells, long capacity) override;
+  ProbeHistory probe_history() override;
+  void clear_probe_history() override;
+  std::vector<long> probe_idx;      // local cell of each probe (-1: another strip's column)
+  long probe_cap = 0, probe_total = 0;
+  std::vector<real> probe_rows;     // [probe_cap][nprobes][PROBE_HISTORY_VARS]
+  std::vector<double> probe_times;  // [probe_cap]
 
   HostArrays h;
   int gi0, gi1;     // owned global columns
@@ -226,6 +259,9 @@ class CpuSolver : public SolverBase {
   std::vector<uint8_t> lb;
   LeanSoA lean_view(bool fromg);
   void lean_materialize();
+
+ protected:
+  void after_step() override;
 };
 
 class RefSolver : public SolverBase {

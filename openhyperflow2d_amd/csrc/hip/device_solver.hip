@@ -44,6 +44,7 @@
 #include "chem_mech.hpp"
 #include "lean_ns.hpp"
 #include "lean_mech.hpp"
+#include "probe_history.hpp"
 
 #define HIP_CHECK(x)                                                                             \
   do {                                                                                           \
@@ -2103,6 +2104,7 @@ struct DeviceSolver::Impl {
   ScenarioTables* scen = nullptr;
   long* probe_idx = nullptr;   // K8 monitor probes (sample_monitors)
   real* probe_out = nullptr;
+  ProbeRing ring{};            // per-step recorder (record_probes); cap == 0: not armed
   DevScalars* sc = nullptr;
   DevScalars* sc_host = nullptr;   // pinned
   bool sc_kernel = true;           // sync_scalars: hf2d_scalars_out instead of a copy (HF2D_SC_KERNEL=0: copy)
@@ -2943,6 +2945,132 @@ void DeviceSolver::sample_monitors(std::vector<MonitorPoint>& mp) {
     mp[q].p = pv;
     mp[q].T = Tv;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Per-step probe recorder (hip/probe_history.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::record_probes(const std::vector<std::pair<int, int>>& cells, long capacity) {
+  check_probe_cells(cells, capacity);
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const int n = (int)cells.size();
+  probe_rec_idx.assign(n, -1);
+  for (int q = 0; q < n; q++) {
+    const int i = cells[q].first, j = cells[q].second;
+    if (i < gi0 || i >= gi1) continue;   // another strip's column
+    const long c = (long)(i - gi0 + l_off) * h.ny + j;
+    // (a trimmed strip rank's Case could not check its flags in check_probe_cells)
+    if (has_all(h.CT[c], CT_SOLID) || !has_all(h.CT[c], CT_NODE_IS_SET))
+      throw std::invalid_argument("record_probes: cell (" + std::to_string(i) + ", " + std::to_string(j) +
+                                  ") is solid or not set");
+    probe_rec_idx[q] = c;
+  }
+  // (outside any capture: flush_pending ran the queued steps, and a capture
+  // only lives inside run_graph)
+  ProbeRing r;
+  r.n = n;
+  r.cap = (int)std::min<long>(capacity, 0x7fffffffL);
+  long* idx = m.mem.alloc<long>(n);
+  r.idx = idx;
+  r.rows = m.mem.alloc<real>((size_t)r.cap * n * PROBE_VARS);
+  r.times = m.mem.alloc<double>((size_t)r.cap);
+  r.count = m.mem.alloc<unsigned long long>(1);
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  HIP_CHECK(hipMemcpyAsync(idx, probe_rec_idx.data(), n * sizeof(long), hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.ring = r;
+  probe_cap = r.cap;
+  probe_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+void DeviceSolver::clear_probe_history() {
+  if (!probe_cap) return;
+  flush_pending();
+  Impl& m = *impl;
+  HIP_CHECK(hipMemsetAsync(m.ring.count, 0, sizeof(unsigned long long), m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+ProbeHistory DeviceSolver::probe_history() {
+  if (!probe_cap) throw std::runtime_error("probe_history: no recorder armed (record_probes)");
+  flush_pending();
+  Impl& m = *impl;
+  const ProbeRing& r = m.ring;
+  const size_t row = (size_t)r.n * PROBE_VARS;
+  unsigned long long total = 0;
+  std::vector<real> rows((size_t)r.cap * row);
+  std::vector<double> tp((size_t)r.cap);
+  HIP_CHECK(hipMemcpyAsync(&total, r.count, sizeof total, hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipMemcpyAsync(rows.data(), r.rows, rows.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipMemcpyAsync(tp.data(), r.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  ProbeHistory H;
+  H.nprobes = r.n;
+  H.total = (long)total;
+  const long cap = r.cap, n = std::min<long>(H.total, cap), first = H.total > cap ? H.total % cap : 0;
+  H.times.resize(n);
+  H.values.resize((size_t)n * row);
+  for (long k = 0; k < n; k++) {
+    const long s = (first + k) % cap;
+    // the device accumulates time since the start; the host's time is
+    // global_time + (time_part - time_offset) (sync_scalars, summary)
+    const real part = tp[s] - time_offset;
+    H.times[k] = cs.global_time + part;
+    std::copy(rows.begin() + s * row, rows.begin() + (s + 1) * row, H.values.begin() + k * row);
+  }
+  H.owned.resize(r.n);
+  for (int q = 0; q < r.n; q++) H.owned[q] = probe_rec_idx[q] >= 0 ? 1 : 0;
+  return H;
+}
+
+// Last launch of a step: the row of every probe from the post-step buffers,
+// in the representation that is authoritative now (the views download() /
+// lns_materialize() would read).
+void DeviceSolver::launch_probe_record(const StepParams& P) {
+  Impl& m = *impl;
+  int kind = PR_GATHER;
+  SoA s;
+  if (lns_state) {
+    // lean N-S / mechanism: Sp^{m+1} and the lagged level (lns_materialize's input view)
+    s = m.view(h, 1 - sbuf, abuf, dsbuf, 1 - pbuf);
+    real* const cpx[2] = {m.CP, m.CP2};
+    real* const mux[2] = {m.mu, m.mu2};
+    real* const lamx[2] = {m.lam, m.lam2};
+    real* const kkx[2] = {m.kk, m.kk2};
+    real* const mutx[2] = {m.mu_t, m.mu_t2};
+    real* const px[2] = {m.p, m.p2};
+    if (m.mech) {
+      kind = PR_MECH;
+      s.kk = kkx[cbuf];          // the lagged k of fill_node's skip test
+      s.Tg = m.Tst[1 - cbuf];    // stored state of the new level
+      s.p = px[1 - cbuf];
+    } else {
+      kind = sk_mode == SK_SGT ? PR_SGT : PR_SGL;
+      s.CP = cpx[1 - cbuf];
+      s.mu = mux[1 - cbuf];
+      s.lam = lamx[1 - cbuf];
+      s.kk = kkx[1 - cbuf];
+      s.mu_t = mutx[1 - cbuf];
+    }
+  } else {
+    s = m.view(h, sbuf, abuf, dsbuf, pbuf);
+    if (lean_state) {
+      s.p = m.P2[pbuf];
+      if (!lean_T_stored) kind = PR_LEAN;
+    }
+  }
+  const dim3 g(1), b(PROBE_MAX);
+  switch (kind) {
+    case PR_SGL: hipLaunchKernelGGL(hf2d_probe_record<PR_SGL>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    case PR_SGT: hipLaunchKernelGGL(hf2d_probe_record<PR_SGT>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    case PR_MECH: hipLaunchKernelGGL(hf2d_probe_record<PR_MECH>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    case PR_LEAN: hipLaunchKernelGGL(hf2d_probe_record<PR_LEAN>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    default: hipLaunchKernelGGL(hf2d_probe_record<PR_GATHER>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+  }
+  HIP_CHECK(hipGetLastError());
 }
 
 void DeviceSolver::poison_cell(int gi, int j) {
@@ -3864,7 +3992,10 @@ uint64_t DeviceSolver::mode_signature() const {
                         (int)lean_ns, (int)lean_mech, sbuf, abuf, dsbuf, pbuf, cbuf,
                         // (settings a captured launch bakes in: the cpt gate and the stagger rounds,
                         // the mailbox push kernel, the dt read, the skipped stores, the ghost prologue)
-                        cu_count, push_per, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue};
+                        cu_count, push_per, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue,
+                        // (a window captured before record_probes has no recorder launch, one
+                        // captured before arming again writes the previous ring)
+                        probe_gen};
   uint64_t h = 0;
   for (int f : fields) h = h * 1000003ull + (uint64_t)(f + 1);
   return h;
@@ -4367,7 +4498,12 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     size_t shmem = (size_t)lean_tile_fields(sg) * T.NC * sizeof(real);
     if (lean_wgcu > 0)   // cap the resident workgroups per CU through the LDS request (160 KB per CU)
       shmem = std::max(shmem, (size_t)((LDS_PER_CU / lean_wgcu - 1024) & ~255));
-    const bool out = step_outputs || want_res;
+    // an armed recorder needs T of every step, which the plain variant does
+    // not store: where R is constant over a tile step (single gas, or no
+    // reactions) the recorder forms it from p, R, rho; a reacting mixture
+    // runs the output variant instead
+    const bool rec_out = probe_cap > 0 && !sg && P.chem_model != NO_REACTIONS;
+    const bool out = step_outputs || want_res || rec_out;
     // staggered start only for a grid that is resident at once (<= 4 dispatch
     // rounds: measured 1.5 us faster on the headline grid; the 4000x1000 triple
     // point, dispatched in ~15 waves, ran 350 -> 550 us with it)
@@ -4401,6 +4537,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
                        !want_res && !out && !tile_trace && lean_occ == 0;
     if (split) {
       lean_tile_last.seen |= 1;   // (the part launches are plain steps)
+      lean_T_stored = false;
       if (!m.comm_stream) {
         HIP_CHECK(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
         HIP_CHECK(hipEventCreateWithFlags(&m.ev_edge, hipEventDisableTiming));
@@ -4438,6 +4575,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
       }
       exchange_dt(slot_next);
       overlap_steps++;
+      if (probe_cap) launch_probe_record(P);
       nstep++;
       StepResult r;
       r.async = true;
@@ -4448,6 +4586,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     const int var = want_res ? 2 : out ? 1 : 0;
     lean_tile_last.var = var;
     lean_tile_last.seen |= 1 << var;
+    lean_T_stored = var != 0;
     if (tile_trace && var == 0 && !fx_step)
       hipLaunchKernelGGL(nt == BLOCK ? kTileTr[sg][cpt - 1] : kTileTrNt[nts][cpt - 1], dim3(ntile), dim3(nt), shmem,
                          st, P, L, T, m.sc, slot, slot_next, serial, m.partials, tile_trace);
@@ -4469,7 +4608,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     else {
       // single GPU, last step of the host call: the scalars go to the host
       // mirror from the kernel's own tail (host_tail)
-      const bool mirror = var == 1 && !tile_trace && host_tail && m.nranks == 1 && !m.local && !m.p2p.on;
+      const bool mirror = var == 1 && step_outputs && !tile_trace && host_tail && m.nranks == 1 && !m.local && !m.p2p.on;
       if (mirror) {
         P.host_sc = m.sc_host;
         P.host_done = m.host_done;
@@ -4509,6 +4648,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     dsbuf = 1 - dsbuf;
     pbuf = 1 - pbuf;
     lean_state = 1;
+    lean_T_stored = true;   // (the flat kernel always writes the output-only fields)
   } else if (euler && fused && !m.mech) {
     if (lean_state) lean_materialize();
     // Predictor and fill of a cell run back to back in one thread, so the
@@ -4686,6 +4826,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     hipLaunchKernelGGL(hf2d_wall_wall, dim3(nblk), dim3(BLOCK), 0, st, P, s, m.qdir, c0, c1, m.sc, slot);
     HIP_CHECK(hipGetLastError());
   }
+  if (probe_cap) launch_probe_record(P);
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;
   StepResult r;
@@ -4824,6 +4965,8 @@ std::string DeviceSolver::autotune(int steps) {
   const bool s_src = isSrcAdd, s_out = step_outputs;
   const ResidualSummary s_res = last_res;
   const bool s_resv = last_res_valid;
+  const long s_probe = probe_cap;   // the trial steps are not the run's: an armed recorder sits them out
+  probe_cap = 0;
   struct Cand {
     int cpt, tj, nt, wgcu = 0;
   };
@@ -4952,6 +5095,7 @@ std::string DeviceSolver::autotune(int steps) {
   step_outputs = s_out;
   last_res = s_res;
   last_res_valid = s_resv;
+  probe_cap = s_probe;
   upload();   // device scalars from the restored host state
   graph_launches = 0;
   lns_steps = lnm_steps = 0;   // (the tuning steps do not count as the run's)

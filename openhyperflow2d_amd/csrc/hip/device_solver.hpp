@@ -98,6 +98,16 @@ class DeviceSolver : public SolverBase {
   void sample_monitors(std::vector<MonitorPoint>& mp) override;
   std::vector<long> probe_idx_host;
   std::vector<real> probe_buf_host;
+  // per-step recorder (hip/probe_history.hpp): hf2d_probe_record is the last
+  // launch of every step while armed; reading the history neither leaves the
+  // lean state nor changes a ping-pong parity
+  void record_probes(const std::vector<std::pair<int, int>>& cells, long capacity) override;
+  ProbeHistory probe_history() override;
+  void clear_probe_history() override;
+  int probe_gen = 0;            // arming generation (mode_signature: a cached window bakes the ring in)
+  long probe_cap = 0;           // 0: not armed
+  std::vector<long> probe_rec_idx;   // local cell of each probe (-1: another strip's column)
+  bool lean_T_stored = true;    // the last lean inviscid step stored T (every kernel but the plain tile variant)
   void trace_push(const char* name) override;
   void trace_pop() override;
   double time_offset = 0.0, last_dev_time = 0.0;
@@ -293,6 +303,7 @@ class DeviceSolver : public SolverBase {
   std::unique_ptr<GraphCache> graph;
   std::vector<StepParams> pending;
   void run_graph();
+  void launch_probe_record(const StepParams& P);   // end of do_step_eager, post-step buffers
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)
   void step_split(const StepParams& P, bool want_res, int slot, int slot_next, int serial, unsigned nblk, bool to_lns);
   bool lns_step_ok(const StepParams& P) const;

@@ -43,6 +43,9 @@ def parse_fault(spec: str):
     return int(kv["step"]), int(kv.get("rank", 0)), kind
 
 
+PROBE_VARS = ("p", "T", "rho", "U", "V")   # column order of Simulation.probe_history()["values"]
+
+
 class Simulation:
     def __init__(self, deck_text: str, backend: Optional[str] = None, *, workdir: str = ".",
                  use_checkpoint: bool = False, device: int = 0, semantics: str = "mpi",
@@ -97,6 +100,45 @@ class Simulation:
     def records(self) -> bytes:
         self.solver.download()
         return self.case.records()
+
+    # -- per-step probe recorder --------------------------------------------
+    def record_probes(self, cells, capacity: int = 4096) -> None:
+        """Arm the per-step recorder on the global cells ``(i, j)`` (at most 64).
+
+        From now on every step appends one row per probe, in the fixed
+        variable order ``PROBE_VARS = ("p", "T", "rho", "U", "V")``, and the
+        step's time to a ring of ``capacity`` rows kept by the backend (on the
+        GPU: in device memory, written by one small kernel at the end of the
+        step, so the steps stay in their graphs and the lean states are never
+        materialised).  Each value is bit for bit what ``field(name)[i, j]``
+        returns after that step.  Arming again replaces the recorder and
+        restarts the count.  ``ValueError``: no cell, more than 64, a cell
+        outside the grid, solid or unset, or ``capacity < 1``."""
+        self.solver.record_probes([(int(i), int(j)) for i, j in cells], int(capacity))
+
+    def probe_history(self) -> dict:
+        """The recorded rows, oldest first: ``times`` [n], ``values``
+        [n, nprobes, 5] (variables in ``PROBE_VARS`` order), ``total`` (steps
+        recorded since arming; n = min(total, capacity), i.e. the last
+        ``capacity`` steps once the ring has wrapped) and ``owned`` [nprobes]
+        (False: the probe's column belongs to another strip and reads 0).
+        ``times[k]`` equals ``summary()["time"]`` after that step.  Reading
+        does not disturb the solver state."""
+        h = dict(self.solver.probe_history())
+        h["times"] = np.asarray(h["times"])
+        h["values"] = np.asarray(h["values"])
+        h["owned"] = np.asarray(h["owned"])
+        h["total"] = int(h["total"])
+        return h
+
+    def clear_probe_history(self) -> None:
+        """Drop the recorded rows; the recorder stays armed on the same cells."""
+        self.solver.clear_probe_history()
+
+    def monitor_cells(self):
+        """The deck's monitor points (NumMonitorPoints / Point-n.X/Y) as the
+        cells the driver samples: ``i = int(x / dx)``, ``j = int(y / dy)``."""
+        return [(int(i), int(j)) for i, j in self.case.monitor_cells]
 
     @property
     def shape(self):
