@@ -6,6 +6,7 @@
                                      [--profile FILE] [--fault-inject step:N,rank:R,kind:nan|kill]
                                      [--transport p2p|rccl]
                                      [--probe-history FILE.npz [--probe-capacity N]]
+                                     [--averages FILE.npz [--averages-every K]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
   python -m openhyperflow2d_amd info deck.dat
   python -m openhyperflow2d_amd build
@@ -44,6 +45,11 @@ def _cmd_run(a) -> int:
             print("--probe-history records in one process only; this is a %d-rank launch "
                   "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
         return 2
+    if a.averages and world > 1:
+        if rank == 0:
+            print("--averages accumulates in one process only; this is a %d-rank launch "
+                  "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
+        return 2
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -77,6 +83,12 @@ def _cmd_run(a) -> int:
         except (ValueError, RuntimeError) as e:
             print("--probe-history: %s" % e, file=sys.stderr, flush=True)
             return 2
+    if a.averages:
+        try:
+            sim.start_averaging(every=a.averages_every)
+        except (ValueError, RuntimeError) as e:
+            print("--averages: %s" % e, file=sys.stderr, flush=True)
+            return 2
     try:
         cycles, log = sim.run(max_cycles=a.cycles, outdir=outdir, outputs=True, checkpoint=not a.no_checkpoint,
                               verbose=True, metrics=a.metrics or "", profile=a.profile or "",
@@ -95,6 +107,16 @@ def _cmd_run(a) -> int:
                      vars=np.asarray(PROBE_VARS), total=np.int64(h["total"]))
         print("probe history: %d of %d steps x %d points -> %s" % (h["values"].shape[0], h["total"], len(probe_cells),
                                                                     a.probe_history), flush=True)
+    if a.averages:
+        import numpy as np
+
+        from .models.simulation import PROBE_VARS
+
+        av = sim.averages()
+        with open(a.averages, "wb") as f:   # (np.savez on a path would append ".npz")
+            np.savez(f, mean=av["mean"], var=av["var"], cov_uv=av["cov_uv"], vars=np.asarray(PROBE_VARS),
+                     time=np.float64(av["time"]), samples=np.int64(av["samples"]))
+        print("averages: %d samples over t = %.6e -> %s" % (av["samples"], av["time"], a.averages), flush=True)
     if rank == 0:
         sys.stdout.write(log)
         print("\nReady. Computation finished (%d cycles)." % cycles, flush=True)
@@ -189,6 +211,12 @@ def main(argv=None) -> int:
                         "and write times / values / cells / vars to this file")
     r.add_argument("--probe-capacity", dest="probe_capacity", type=int, default=4096, metavar="N",
                    help="rows the recorder keeps: the last N steps (default 4096)")
+    r.add_argument("--averages", metavar="FILE.npz",
+                   help="accumulate time-averaged p, T, rho, U, V, their variances and the U-V covariance over the "
+                        "whole field at every step (one process only) and write mean / var / cov_uv / vars / time / "
+                        "samples to this file")
+    r.add_argument("--averages-every", dest="averages_every", type=int, default=1, metavar="K",
+                   help="sample every K-th step (default 1)")
     d = sub.add_parser("deck", help="write a generated deck")
     d.add_argument("name")
     d.add_argument("--nx", type=int)

@@ -655,6 +655,37 @@ PYBIND11_MODULE(_hf2d, m) {
              return d;
            })
       .def("clear_probe_history", &SolverBase::clear_probe_history)
+      .def("start_averaging", &SolverBase::start_averaging, py::arg("every") = 1, py::arg("second_moments") = true,
+           py::arg("step_weight") = false,
+           "arm the whole-field accumulator: weighted running mean (and variances, U-V covariance) of "
+           "(p, T, rho, U, V) over every `every`-th step")
+      .def("reset_averaging", &SolverBase::reset_averaging)
+      .def("stop_averaging", &SolverBase::stop_averaging)
+      .def("averages",
+           [](SolverBase& s) {
+             FlowAverages A;
+             {
+               py::gil_scoped_release rel;
+               A = s.averages();
+             }
+             const py::ssize_t nxl = A.gi1 - A.gi0, ny = A.ny;
+             py::dict d;
+             py::array_t<double> mean(std::vector<py::ssize_t>{(py::ssize_t)STATS_VARS, nxl, ny});
+             std::copy(A.mean.begin(), A.mean.end(), mean.mutable_data());
+             d["mean"] = mean;
+             if (A.second_moments) {
+               py::array_t<double> var(std::vector<py::ssize_t>{(py::ssize_t)STATS_VARS, nxl, ny});
+               py::array_t<double> cov(std::vector<py::ssize_t>{nxl, ny});
+               std::copy(A.var.begin(), A.var.end(), var.mutable_data());
+               std::copy(A.cov_uv.begin(), A.cov_uv.end(), cov.mutable_data());
+               d["var"] = var;
+               d["cov_uv"] = cov;
+             }
+             d["time"] = A.time;
+             d["samples"] = A.samples;
+             d["columns"] = py::make_tuple(A.gi0, A.gi1);
+             return d;
+           })
       .def("sample_monitors",
            [](SolverBase& s) {   // the driver's output-step sampling of the deck's monitor points: [(p, T)]
              s.sample_monitors(s.cs.cfg.monitors);

@@ -451,6 +451,13 @@ void SolverBase::record_probes(const std::vector<std::pair<int, int>>&, long) {
 ProbeHistory SolverBase::probe_history() { throw std::runtime_error("this backend has no per-step probe recorder"); }
 void SolverBase::clear_probe_history() {}
 
+void SolverBase::start_averaging(int, bool, bool) {
+  throw std::runtime_error("this backend has no flow-statistics accumulator");
+}
+void SolverBase::reset_averaging() {}
+void SolverBase::stop_averaging() {}
+FlowAverages SolverBase::averages() { throw std::runtime_error("this backend has no flow-statistics accumulator"); }
+
 void SolverBase::sample_monitors(std::vector<MonitorPoint>& mp) {
   if (mp.empty()) return;
   Field& J = cs.J;
@@ -827,7 +834,62 @@ void CpuSolver::clear_probe_history() { probe_total = 0; }
 
 // the values download() would put into the records now: the lean inviscid
 // state keeps its pressure in P2 (lean_materialize_cell copies it to p)
+void CpuSolver::start_averaging(int every, bool second_moments, bool step_weight) {
+  if (every < 1) throw std::invalid_argument("start_averaging: every must be at least 1");
+  avg_sc = StatsScalars{};
+  avg_sc.every = every;
+  avg_sc.step_weight = step_weight ? 1 : 0;
+  avg_second = second_moments;
+  avg_m.assign((size_t)STATS_VARS * h.N, 0.0);
+  avg_M.assign(second_moments ? (size_t)STATS_VARS * h.N : 0, 0.0);
+  avg_C.assign(second_moments ? (size_t)h.N : 0, 0.0);
+  avg_sc.t_seen = (double)(cs.global_time + cur_time_part);
+  avg_on = avg_armed = true;
+}
+
+void CpuSolver::reset_averaging() {
+  if (!avg_on) return;
+  start_averaging(avg_sc.every, avg_second, avg_sc.step_weight != 0);
+}
+
+void CpuSolver::stop_averaging() { avg_on = false; }
+
+FlowAverages CpuSolver::averages() {
+  if (!avg_armed) throw std::runtime_error("averages: no accumulator armed (start_averaging)");
+  FlowAverages A;
+  A.gi0 = gi0;
+  A.gi1 = gi1;
+  A.ny = h.ny;
+  A.second_moments = avg_second;
+  A.time = avg_sc.W;
+  A.samples = (long)avg_sc.samples;
+  const long c0 = (long)l_off * h.ny, n = (long)(gi1 - gi0) * h.ny;
+  auto planes = [&](const std::vector<double>& src, int np, std::vector<double>& dst) {
+    dst.resize((size_t)np * n);
+    for (int k = 0; k < np; k++) std::copy(src.begin() + k * h.N + c0, src.begin() + k * h.N + c0 + n, dst.begin() + k * n);
+  };
+  planes(avg_m, STATS_VARS, A.mean);
+  if (avg_second) {
+    planes(avg_M, STATS_VARS, A.var);
+    planes(avg_C, 1, A.cov_uv);
+    A.finish(avg_sc.W);
+  }
+  return A;
+}
+
 void CpuSolver::after_step() {
+  if (avg_on && stats_tick(avg_sc, (double)(cs.global_time + cur_time_part))) {
+    const real* p = lean_state ? P2[pbuf].data() : h.p.data();
+    const long c0 = (long)l_off * h.ny, c1 = c0 + (long)(gi1 - gi0) * h.ny;
+    for (long c = c0; c < c1; c++) {
+      if (has_all(h.CT[c], CT_SOLID) || !has_all(h.CT[c], CT_NODE_IS_SET)) continue;
+      const real row[STATS_VARS] = {p[c], h.Tg[pbuf][c], h.S[0][c], h.U[pbuf][c], h.V[pbuf][c]};
+      if (avg_second)
+        stats_cell<true>(avg_sc.w, avg_sc.r, row, &avg_m[c], &avg_M[c], &avg_C[c], h.N);
+      else
+        stats_cell<false>(avg_sc.w, avg_sc.r, row, &avg_m[c], nullptr, nullptr, h.N);
+    }
+  }
   if (probe_cap == 0) return;
   const size_t np = probe_idx.size();
   const long slot = probe_total % probe_cap;

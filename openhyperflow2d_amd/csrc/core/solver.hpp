@@ -21,6 +21,7 @@
 #include "case.hpp"
 #include "residual.hpp"
 #include "lean_euler.hpp"
+#include "flow_stats.hpp"
 
 namespace hf2d {
 
@@ -94,6 +95,24 @@ struct ProbeHistory {
   std::vector<double> times;      // [n] time after the step (summary()["time"])
   std::vector<real> values;       // [n][nprobes][PROBE_HISTORY_VARS]
   std::vector<uint8_t> owned;     // [nprobes] 1: this backend owns the probe's column (others read 0)
+};
+
+// Time-averaged flow statistics (start_averaging): planes over the owned
+// columns [gi0, gi1), x-major like the state; solid / unset cells stay 0.
+struct FlowAverages {
+  int gi0 = 0, gi1 = 0, ny = 0;
+  bool second_moments = false;
+  double time = 0.0;             // weight sum W: the averaged time span (step weight: the sample count)
+  long samples = 0;
+  std::vector<double> mean;      // [STATS_VARS][nxl][ny]
+  std::vector<double> var;       // [STATS_VARS][nxl][ny]  M / W (second moments only)
+  std::vector<double> cov_uv;    // [nxl][ny]              C / W (second moments only)
+  // M, C -> var, cov_uv: the IEEE division by W (0 before the first sample)
+  void finish(double W) {
+    if (!(W > 0.0)) return;
+    for (double& x : var) x = x / W;
+    for (double& x : cov_uv) x = x / W;
+  }
 };
 
 struct RunOptions {
@@ -183,6 +202,20 @@ class SolverBase {
   virtual void clear_probe_history();
   void check_probe_cells(const std::vector<std::pair<int, int>>& cells, long capacity) const;
 
+  // Opt-in whole-field statistics (core/flow_stats.hpp): every `every`-th
+  // step the row (p, T, rho, U, V) of each owned gas cell, as a download
+  // after that step yields it, enters a running weighted mean and, with
+  // second_moments, the variances and the U, V covariance.  The weight is the
+  // time since the previous sample (step_weight: 1).  Starting again, also
+  // with other options, restarts from zero; reset keeps the options; stop
+  // freezes the result, which averages() still returns.
+  // std::invalid_argument: every < 1.  std::runtime_error: averages() before
+  // any start, or a backend without an accumulator.
+  virtual void start_averaging(int every, bool second_moments, bool step_weight);
+  virtual void reset_averaging();
+  virtual void stop_averaging();
+  virtual FlowAverages averages();
+
  protected:
   // called by advance() after a step the host completed (not the device's asynchronous ones)
   virtual void after_step() {}
@@ -229,6 +262,14 @@ class CpuSolver : public SolverBase {
   long probe_cap = 0, probe_total = 0;
   std::vector<real> probe_rows;     // [probe_cap][nprobes][PROBE_HISTORY_VARS]
   std::vector<double> probe_times;  // [probe_cap]
+  // host accumulator: the arrays the probe recorder reads, after each step
+  void start_averaging(int every, bool second_moments, bool step_weight) override;
+  void reset_averaging() override;
+  void stop_averaging() override;
+  FlowAverages averages() override;
+  StatsScalars avg_sc;
+  bool avg_on = false, avg_armed = false, avg_second = false;   // armed: planes exist (on, or stopped)
+  std::vector<double> avg_m, avg_M, avg_C;   // [STATS_VARS][N], [STATS_VARS][N], [N]
 
   HostArrays h;
   int gi0, gi1;     // owned global columns

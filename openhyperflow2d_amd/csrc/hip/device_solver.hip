@@ -45,6 +45,7 @@
 #include "lean_ns.hpp"
 #include "lean_mech.hpp"
 #include "probe_history.hpp"
+#include "flow_stats.hpp"
 
 #define HIP_CHECK(x)                                                                             \
   do {                                                                                           \
@@ -2105,6 +2106,8 @@ struct DeviceSolver::Impl {
   long* probe_idx = nullptr;   // K8 monitor probes (sample_monitors)
   real* probe_out = nullptr;
   ProbeRing ring{};            // per-step recorder (record_probes); cap == 0: not armed
+  FlowStats stats{};           // whole-field statistics (start_averaging)
+  size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
   DevScalars* sc = nullptr;
   DevScalars* sc_host = nullptr;   // pinned
   bool sc_kernel = true;           // sync_scalars: hf2d_scalars_out instead of a copy (HF2D_SC_KERNEL=0: copy)
@@ -2752,6 +2755,14 @@ void DeviceSolver::upload() {
   *m.sc_host = s0;
   cp(m.sc, m.sc_host, sizeof(DevScalars));
   m.sc_mirrored = false;
+  // the accumulator's clock is time_part - t_off, the host's cur_time_part:
+  // it goes on from the host's value across the restart of time_part, and no
+  // sample is weighted across an upload
+  const double st_clock[2] = {(double)cur_time_part, time_offset};
+  if (stats_armed) {
+    static_assert(offsetof(StatsScalars, t_seen) + sizeof(double) == offsetof(StatsScalars, t_off), "adjacent");
+    cp(&m.stats.sc->t_seen, st_clock, sizeof st_clock);
+  }
   HIP_CHECK(hipStreamSynchronize(st));
   nstep = 0;
   abuf = 0;
@@ -3029,10 +3040,9 @@ ProbeHistory DeviceSolver::probe_history() {
 // Last launch of a step: the row of every probe from the post-step buffers,
 // in the representation that is authoritative now (the views download() /
 // lns_materialize() would read).
-void DeviceSolver::launch_probe_record(const StepParams& P) {
-  Impl& m = *impl;
+int DeviceSolver::post_step_view(SoA& s) const {
+  const Impl& m = *impl;
   int kind = PR_GATHER;
-  SoA s;
   if (lns_state) {
     // lean N-S / mechanism: Sp^{m+1} and the lagged level (lns_materialize's input view)
     s = m.view(h, 1 - sbuf, abuf, dsbuf, 1 - pbuf);
@@ -3062,6 +3072,13 @@ void DeviceSolver::launch_probe_record(const StepParams& P) {
       if (!lean_T_stored) kind = PR_LEAN;
     }
   }
+  return kind;
+}
+
+void DeviceSolver::launch_probe_record(const StepParams& P) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
   const dim3 g(1), b(PROBE_MAX);
   switch (kind) {
     case PR_SGL: hipLaunchKernelGGL(hf2d_probe_record<PR_SGL>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
@@ -3069,6 +3086,122 @@ void DeviceSolver::launch_probe_record(const StepParams& P) {
     case PR_MECH: hipLaunchKernelGGL(hf2d_probe_record<PR_MECH>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
     case PR_LEAN: hipLaunchKernelGGL(hf2d_probe_record<PR_LEAN>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
     default: hipLaunchKernelGGL(hf2d_probe_record<PR_GATHER>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Whole-field time averages (hip/flow_stats.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::start_averaging(int every, bool second_moments, bool step_weight) {
+  if (every < 1) throw std::invalid_argument("start_averaging: every must be at least 1");
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const size_t N = (size_t)h.N, planes = second_moments ? 2 * STATS_VARS + 1 : STATS_VARS;
+  FlowStats f = m.stats;
+  if (planes > m.stats_planes) {   // (arming again with as many planes or fewer reuses them)
+    f.m = m.mem.alloc<double>(planes * N);
+    m.stats_planes = planes;
+  }
+  if (!f.sc) f.sc = m.mem.alloc<StatsScalars>(1);
+  f.M = second_moments ? f.m + STATS_VARS * N : nullptr;
+  f.C = second_moments ? f.m + 2 * STATS_VARS * N : nullptr;
+  f.c0 = (long)l_off * h.ny;
+  f.c1 = f.c0 + (long)(gi1 - gi0) * h.ny;
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  StatsScalars s0{};
+  s0.every = every;
+  s0.step_weight = step_weight ? 1 : 0;
+  s0.t_off = time_offset;
+  HIP_CHECK(hipMemcpyAsync(f.sc, &s0, sizeof s0, hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipMemsetAsync(f.m, 0, planes * N * sizeof(double), m.stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, f.sc, m.sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.stats = f;
+  stats_second = second_moments;
+  stats_on = stats_armed = true;
+  stats_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+void DeviceSolver::reset_averaging() {
+  if (!stats_on) return;
+  flush_pending();
+  Impl& m = *impl;
+  const size_t planes = stats_second ? 2 * STATS_VARS + 1 : STATS_VARS;
+  HIP_CHECK(hipMemsetAsync(m.stats.m, 0, planes * (size_t)h.N * sizeof(double), m.stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, m.stats.sc, m.sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+void DeviceSolver::stop_averaging() {
+  if (!stats_on) return;
+  flush_pending();
+  stats_on = false;
+  stats_gen++;   // the cached windows hold the accumulate nodes
+}
+
+FlowAverages DeviceSolver::averages() {
+  if (!stats_armed) throw std::runtime_error("averages: no accumulator armed (start_averaging)");
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const FlowStats& f = m.stats;
+  FlowAverages A;
+  A.gi0 = gi0;
+  A.gi1 = gi1;
+  A.ny = h.ny;
+  A.second_moments = stats_second;
+  const size_t n = (size_t)(f.c1 - f.c0), N = (size_t)h.N;
+  StatsScalars sc;
+  HIP_CHECK(hipMemcpyAsync(&sc, f.sc, sizeof sc, hipMemcpyDeviceToHost, m.stream));
+  auto planes = [&](const double* src, int np, std::vector<double>& dst) {
+    dst.resize((size_t)np * n);
+    for (int k = 0; k < np; k++)
+      HIP_CHECK(hipMemcpyAsync(dst.data() + k * n, src + k * N + f.c0, n * sizeof(double), hipMemcpyDeviceToHost,
+                               m.stream));
+  };
+  planes(f.m, STATS_VARS, A.mean);
+  if (stats_second) {
+    planes(f.M, STATS_VARS, A.var);
+    planes(f.C, 1, A.cov_uv);
+  }
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  A.time = sc.W;
+  A.samples = (long)sc.samples;
+  if (stats_second) A.finish(sc.W);
+  return A;
+}
+
+// After the recorder's launch: the tick decides on the device whether the
+// step is a sample and forms its weight; the cell pass reads the same view
+// the recorder reads.  Nothing here allocates, copies or synchronises.
+template <int KIND>
+static void launch_stats_kind(hipStream_t st, unsigned nblk, bool second, const StepParams& P, const SoA& s,
+                              const FlowStats& f) {
+  if (second)
+    hipLaunchKernelGGL((hf2d_stats_accum<KIND, true>), dim3(nblk), dim3(STATS_BLOCK), 0, st, P, s, f);
+  else
+    hipLaunchKernelGGL((hf2d_stats_accum<KIND, false>), dim3(nblk), dim3(STATS_BLOCK), 0, st, P, s, f);
+}
+
+void DeviceSolver::launch_stats(const StepParams& P) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
+  const FlowStats& f = m.stats;
+  hipLaunchKernelGGL(hf2d_stats_tick, dim3(1), dim3(64), 0, m.stream, f.sc, m.sc);
+  HIP_CHECK(hipGetLastError());
+  const unsigned nblk = (unsigned)((f.c1 - f.c0 + STATS_BLOCK - 1) / STATS_BLOCK);
+  switch (kind) {
+    case PR_SGL: launch_stats_kind<PR_SGL>(m.stream, nblk, stats_second, P, s, f); break;
+    case PR_SGT: launch_stats_kind<PR_SGT>(m.stream, nblk, stats_second, P, s, f); break;
+    case PR_MECH: launch_stats_kind<PR_MECH>(m.stream, nblk, stats_second, P, s, f); break;
+    case PR_LEAN: launch_stats_kind<PR_LEAN>(m.stream, nblk, stats_second, P, s, f); break;
+    default: launch_stats_kind<PR_GATHER>(m.stream, nblk, stats_second, P, s, f); break;
   }
   HIP_CHECK(hipGetLastError());
 }
@@ -3995,7 +4128,9 @@ uint64_t DeviceSolver::mode_signature() const {
                         cu_count, push_per, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue,
                         // (a window captured before record_probes has no recorder launch, one
                         // captured before arming again writes the previous ring)
-                        probe_gen};
+                        probe_gen,
+                        // (likewise the accumulator's two launches: start / stop_averaging)
+                        stats_gen};
   uint64_t h = 0;
   for (int f : fields) h = h * 1000003ull + (uint64_t)(f + 1);
   return h;
@@ -4502,7 +4637,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     // not store: where R is constant over a tile step (single gas, or no
     // reactions) the recorder forms it from p, R, rho; a reacting mixture
     // runs the output variant instead
-    const bool rec_out = probe_cap > 0 && !sg && P.chem_model != NO_REACTIONS;
+    const bool rec_out = (probe_cap > 0 || stats_on) && !sg && P.chem_model != NO_REACTIONS;
     const bool out = step_outputs || want_res || rec_out;
     // staggered start only for a grid that is resident at once (<= 4 dispatch
     // rounds: measured 1.5 us faster on the headline grid; the 4000x1000 triple
@@ -4576,6 +4711,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
       exchange_dt(slot_next);
       overlap_steps++;
       if (probe_cap) launch_probe_record(P);
+      if (stats_on) launch_stats(P);
       nstep++;
       StepResult r;
       r.async = true;
@@ -4827,6 +4963,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
     HIP_CHECK(hipGetLastError());
   }
   if (probe_cap) launch_probe_record(P);
+  if (stats_on) launch_stats(P);
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;
   StepResult r;
@@ -4967,6 +5104,8 @@ std::string DeviceSolver::autotune(int steps) {
   const bool s_resv = last_res_valid;
   const long s_probe = probe_cap;   // the trial steps are not the run's: an armed recorder sits them out
   probe_cap = 0;
+  const bool s_stats = stats_on;   // (nor does the accumulator take them as samples)
+  stats_on = false;
   struct Cand {
     int cpt, tj, nt, wgcu = 0;
   };
@@ -5096,6 +5235,7 @@ std::string DeviceSolver::autotune(int steps) {
   last_res = s_res;
   last_res_valid = s_resv;
   probe_cap = s_probe;
+  stats_on = s_stats;
   upload();   // device scalars from the restored host state
   graph_launches = 0;
   lns_steps = lnm_steps = 0;   // (the tuning steps do not count as the run's)

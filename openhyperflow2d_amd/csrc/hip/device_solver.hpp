@@ -107,6 +107,17 @@ class DeviceSolver : public SolverBase {
   int probe_gen = 0;            // arming generation (mode_signature: a cached window bakes the ring in)
   long probe_cap = 0;           // 0: not armed
   std::vector<long> probe_rec_idx;   // local cell of each probe (-1: another strip's column)
+  // whole-field statistics (hip/flow_stats.hpp): hf2d_stats_tick and
+  // hf2d_stats_accum follow the recorder's launch while armed; reading the
+  // averages neither leaves the lean state nor changes a ping-pong parity
+  void start_averaging(int every, bool second_moments, bool step_weight) override;
+  void reset_averaging() override;
+  void stop_averaging() override;
+  FlowAverages averages() override;
+  bool stats_on = false;        // the two kernels are launched
+  bool stats_armed = false;     // planes exist (on, or stopped: averages() reads the frozen result)
+  bool stats_second = false;
+  int stats_gen = 0;            // arming generation (mode_signature, as probe_gen)
   bool lean_T_stored = true;    // the last lean inviscid step stored T (every kernel but the plain tile variant)
   void trace_push(const char* name) override;
   void trace_pop() override;
@@ -304,6 +315,8 @@ class DeviceSolver : public SolverBase {
   std::vector<StepParams> pending;
   void run_graph();
   void launch_probe_record(const StepParams& P);   // end of do_step_eager, post-step buffers
+  void launch_stats(const StepParams& P);          // after it
+  int post_step_view(SoA& s) const;                // PR_* kind and view both of them read
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)
   void step_split(const StepParams& P, bool want_res, int slot, int slot_next, int serial, unsigned nblk, bool to_lns);
   bool lns_step_ok(const StepParams& P) const;

@@ -135,6 +135,58 @@ class Simulation:
         """Drop the recorded rows; the recorder stays armed on the same cells."""
         self.solver.clear_probe_history()
 
+    # -- time-averaged flow statistics ---------------------------------------
+    def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time") -> None:
+        """Arm the whole-field accumulator.
+
+        From now on every ``every``-th step (the first one ``every`` steps
+        from here) folds ``(p, T, rho, U, V)`` of each owned gas cell, bit for
+        bit what ``field(name)`` returns after that step, into a running
+        weighted mean and, with ``second_moments``, the variances and the
+        Reynolds shear stress u'v'.  All sums are float64 and follow the
+        weighted incremental update of West / Welford::
+
+            w = t_now - t_seen;  W1 = W + w;  r = w / W1;  W = W1
+            d = x - m;  m = m + r * d;  e = x - m
+            M = M + (w * d) * e;  C = C + (w * d_U) * e_V
+
+        ``weight="time"`` weights a sample by the time since the previous one
+        (since arming for the first), so ``every=k`` is a time-weighted average
+        of every k-th state; ``weight="step"`` uses ``w = 1``.  On the GPU two
+        small kernels run at the end of each step, inside the step graphs, and
+        the lean states are never materialised.  Starting again restarts from
+        zero.  ``ValueError``: ``every < 1`` or an unknown ``weight``."""
+        if weight not in ("time", "step"):
+            raise ValueError("start_averaging: weight must be 'time' or 'step', not %r" % (weight,))
+        if int(every) < 1:
+            raise ValueError("start_averaging: every must be at least 1")
+        self.solver.start_averaging(int(every), bool(second_moments), weight == "step")
+
+    def averages(self) -> dict:
+        """The accumulated statistics over the owned columns: ``mean``
+        [5, nxl, ny] in ``PROBE_VARS`` order; with second moments ``var``
+        [5, nxl, ny] = M / W and ``cov_uv`` [nxl, ny] = C / W; ``time`` (W: the
+        averaged time span, or the sample count for ``weight="step"``),
+        ``samples`` and ``columns`` = (gi0, gi1).  Solid cells are 0; before
+        the first sample everything is 0.  Reading does not disturb the solver
+        state.  ``RuntimeError`` when no accumulator was started."""
+        a = dict(self.solver.averages())
+        for k in ("mean", "var", "cov_uv"):
+            if k in a:
+                a[k] = np.asarray(a[k])
+        a["time"] = float(a["time"])
+        a["samples"] = int(a["samples"])
+        a["columns"] = tuple(int(c) for c in a["columns"])
+        return a
+
+    def reset_averaging(self) -> None:
+        """Restart the accumulation from zero with the same options."""
+        self.solver.reset_averaging()
+
+    def stop_averaging(self) -> None:
+        """Stop accumulating; ``averages()`` keeps returning the frozen result."""
+        self.solver.stop_averaging()
+
     def monitor_cells(self):
         """The deck's monitor points (NumMonitorPoints / Point-n.X/Y) as the
         cells the driver samples: ``i = int(x / dx)``, ``j = int(y / dy)``."""
