@@ -141,4 +141,42 @@ __device__ inline void scenario_next(const StepParams& P, DevScalars* sc, int sl
   }
 }
 
+constexpr int BLOCK = 256;
+constexpr int WAVE = 64;
+
+// ---------------------------------------------------------------------------
+// Wave-level residual reduction helpers
+// ---------------------------------------------------------------------------
+__device__ inline void shfl_merge(ResidualPack& r, int off) {
+#pragma unroll
+  for (int k = 0; k < NEQ; k++) {
+    EqResidual o;
+    o.dd_max = __shfl_xor(r.eq[k].dd_max, off, WAVE);
+    o.i = __shfl_xor(r.eq[k].i, off, WAVE);
+    o.j = __shfl_xor(r.eq[k].j, off, WAVE);
+    o.rms = __shfl_xor(r.eq[k].rms, off, WAVE);
+    o.sum_div = __shfl_xor(r.eq[k].sum_div, off, WAVE);
+    o.count = __shfl_xor(r.eq[k].count, off, WAVE);
+    EqResidual& f = r.eq[k];
+    const bool later = (o.i > f.i) || (o.i == f.i && o.j > f.j);
+    if (o.dd_max > f.dd_max || (o.dd_max == f.dd_max && later)) {
+      f.dd_max = o.dd_max;
+      f.i = o.i;
+      f.j = o.j;
+    }
+    f.rms += o.rms;
+    f.sum_div += o.sum_div;
+    f.count += o.count;
+  }
+}
+
+// Workgroups are dispatched round-robin over the 8 XCDs (each with its own
+// L2).  Remap so XCD x owns a contiguous run of tiles: the i+-1 neighbour
+// columns a tile reads then sit in the same L2.  Bijective on [0, n).
+constexpr unsigned NUM_XCD = 8;
+__device__ inline unsigned xcd_remap(unsigned b, unsigned n) {
+  const unsigned q = n / NUM_XCD;
+  if (b >= q * NUM_XCD) return b;
+  return (b % NUM_XCD) * q + b / NUM_XCD;
+}
 }  // namespace hf2d

@@ -2,18 +2,16 @@
 // kernel per DEEPS phase, RCCL halo exchange / reductions for strip-
 // decomposed multi-GPU runs.
 //
-// Kernels (rocprof names):
-//   hf2d_predict<RES>     pass 1 + 2a (predictor, BC, residual, blending factor)
-//   hf2d_fill             pass 2b/2c (gradients, FillNode2D, dt, chemistry)
-//   hf2d_fused_euler      predict + fill in one sweep for Euler problems
-//   hf2d_lean_euler       inviscid step on the reduced state (lean_euler.hpp):
-//                         fluxes recomputed from neighbour state, ~1/5 the
-//                         HBM traffic of predict+fill
-//   hf2d_lean_materialize rebuild A/B/F/p from the lean state
-//   hf2d_wall_solid/_wall owner-computes wall heat sources (K5)
-//   hf2d_reduce_residual  deterministic tree over per-wave residual partials (K6)
-//   hf2d_pack/unpack      halo column packing (K7)
-//   hf2d_yplus            per-cycle y+ (K10)
+// Kernel families of this translation unit, by file:
+//   device_solver.hip   split predict / fill, fused and flat lean Euler,
+//                       materialize, wall heat, y+, residual reduction, and
+//                       the lean N-S / mechanism step kernels (hf2d_lns_step*, hf2d_lnm_*)
+//   lean_tile.hpp       inviscid lean tile kernels (hf2d_lean_tile*), fused exchange
+//   halo_kernels.hpp    halo pack / unpack, dt fold, xGMI mailbox kernels (hf2d_p2p_*)
+//   lean_ns.hpp         lean N-S tile step: arrays, LDS layout, per-cell functions
+//   lean_mech.hpp       lean mechanism tile step: likewise
+//   probe_history.hpp   per-step probe recorder
+//   flow_stats.hpp      time-averaged flow statistics
 // dt never leaves the device inside the inner loop: hf2d_fill folds the
 // local CFL limit into a device slot with an integer atomicMin on the IEEE
 // bits (valid for positive doubles, order independent => deterministic) and
@@ -42,6 +40,8 @@
 #include "chem_fast.hpp"
 #include "chem_rtc.hpp"
 #include "chem_mech.hpp"
+#include "lean_tile.hpp"
+#include "halo_kernels.hpp"
 #include "lean_ns.hpp"
 #include "lean_mech.hpp"
 #include "probe_history.hpp"
@@ -64,47 +64,9 @@
 
 namespace hf2d {
 
-constexpr int BLOCK = 256;
-constexpr int WAVE = 64;
-
-// ---------------------------------------------------------------------------
-// Wave-level residual reduction helpers
-// ---------------------------------------------------------------------------
-__device__ inline void shfl_merge(ResidualPack& r, int off) {
-#pragma unroll
-  for (int k = 0; k < NEQ; k++) {
-    EqResidual o;
-    o.dd_max = __shfl_xor(r.eq[k].dd_max, off, WAVE);
-    o.i = __shfl_xor(r.eq[k].i, off, WAVE);
-    o.j = __shfl_xor(r.eq[k].j, off, WAVE);
-    o.rms = __shfl_xor(r.eq[k].rms, off, WAVE);
-    o.sum_div = __shfl_xor(r.eq[k].sum_div, off, WAVE);
-    o.count = __shfl_xor(r.eq[k].count, off, WAVE);
-    EqResidual& f = r.eq[k];
-    const bool later = (o.i > f.i) || (o.i == f.i && o.j > f.j);
-    if (o.dd_max > f.dd_max || (o.dd_max == f.dd_max && later)) {
-      f.dd_max = o.dd_max;
-      f.i = o.i;
-      f.j = o.j;
-    }
-    f.rms += o.rms;
-    f.sum_div += o.sum_div;
-    f.count += o.count;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Kernels
 // ---------------------------------------------------------------------------
-// Workgroups are dispatched round-robin over the 8 XCDs (each with its own
-// L2).  Remap so XCD x owns a contiguous run of tiles: the i+-1 neighbour
-// columns a tile reads then sit in the same L2.  Bijective on [0, n).
-constexpr unsigned NUM_XCD = 8;
-__device__ inline unsigned xcd_remap(unsigned b, unsigned n) {
-  const unsigned q = n / NUM_XCD;
-  if (b >= q * NUM_XCD) return b;
-  return (b % NUM_XCD) * q + b / NUM_XCD;
-}
 // Split kernels (one cell per thread, x-major): logical block of this
 // workgroup.  A column of a tall grid spans a few blocks, so the left/right
 // neighbour reads of the round-robin order land on another XCD's L2; with
@@ -319,586 +281,6 @@ __global__ __launch_bounds__(BLOCK) void hf2d_lean_euler(StepParams P, LeanSoA L
     if (serial) m = fmin(m, P.dt);
     dt_min(sc, slot_next, m);
   }
-}
-
-// Halo pack: nf field columns (each ny contiguous doubles at src[f] + col*ny)
-constexpr int MAX_HALO_FIELDS = 128;   // 4*NEQ + 5 state fields + up to 16 species x 4
-// Halo field list: entry f is column (first + o[f]) / (last - o[f]) of
-// field f on the sending side and ghost column (ghostL - o[f]) / (ghostR +
-// o[f]) on the receiving side: o = 1 carries the second column of a
-// two-column halo (the lean N-S / mechanism kernels on strips).
-struct ColList {
-  real* f[MAX_HALO_FIELDS];
-  unsigned char o[MAX_HALO_FIELDS] = {};
-  int nf;
-};
-constexpr long P2P_SPIN_LIMIT = 1L << 26;   // ~3 s of s_sleep polling, then give up (neg_T bit 2)
-constexpr int P2P_THREADS = 512;
-
-// Acquire load of a peer's publication flag at system scope: the poll loops
-// spin with relaxed loads (cheap) and finish with this one, so every later
-// load (mailbox data, peer dt) is ordered after the observed flag.
-__device__ inline unsigned long long p2p_acquire(const unsigned long long* f) {
-  return __hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__device__ inline double p2p_load(const double* p) {
-  return __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_SYSTEM));
-}
-// (FP32 build: the halo values are floats; the dt words stay doubles)
-__device__ inline float p2p_load(const float* p) {
-  return __int_as_float((int)__hip_atomic_load((const unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-}
-
-// Multi-GPU exchange fused into the lean tile kernel (xGMI mailboxes, see
-// hf2d_p2p_xchg for the layout and the parity argument).  Step s of a rank:
-//   start  the dt slot already holds the global MIN (folded by the previous
-//          kernel's last workgroup); tiles at the strip edges stage their
-//          ghost column straight from the mailbox of parity s-1;
-//   end    cells of the first / last owned column store their new lean
-//          state into the neighbour's mailbox of parity s with
-//          system-coherent stores and wait for their completion (vmcnt);
-//          the last workgroup to finish (completion counter) sends this
-//          rank's local dt MIN to every peer, publishes flag s, waits
-//          (bounded) for the peers' flag s and folds their dt into the slot.
-// One kernel per step and a single waiting workgroup, at the tail: no
-// exchange kernel, no pack/unpack pass, no host involvement, and no
-// system-scope fence (L2 writeback / invalidate) in the other workgroups.
-// Ghost columns of the state arrays are only refreshed by
-// hf2d_p2p_complete, which the host runs before any other consumer.
-__device__ inline void p2p_store(double* p, double v) {
-  __hip_atomic_store((unsigned long long*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ inline void p2p_store(float* p, float v) {
-  __hip_atomic_store((unsigned*)p, (unsigned)__float_as_int(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// outstanding vector-memory operations of this wave (stores included on gfx9)
-// have completed: the ordering point for the relaxed system-coherent stores
-__device__ inline void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ inline unsigned long long rt_clock() { return __builtin_amdgcn_s_memrealtime(); }
-constexpr int FX_DONE_STRIDE = 32;   // completion counters on lines of their own
-// tail phase trace (HF2D_FX_SKIP bit 4, loopback timing runs only): after the
-// counters, FX_TRACE_N records of FX_TRACE_W clocks, one per step (seq mod N)
-constexpr int FX_TRACE_N = 64, FX_TRACE_W = 8;
-constexpr unsigned FX_COUNT1_MAX = 512;
-constexpr int FX_DONE_WORDS = (DT_SHARDS + 1) * FX_DONE_STRIDE + 2 * FX_TRACE_N * FX_TRACE_W;
-struct FusedX {
-  real* peer_recv_l;   // left neighbour's mailbox recv base (we are its right side)
-  real* peer_recv_r;
-  const real* my_recv;
-  unsigned long long* const* peer_flags;
-  double* const* peer_dtr;
-  const unsigned long long* my_flags;
-  const double* my_dtr;
-  unsigned long long* seq;   // last published sequence number
-  unsigned* done;            // workgroups finished in this step: per dt shard, then the shards (FX_DONE_STRIDE apart)
-  long cap;
-  int rank, nranks, sides, on;
-  // lagged dt: the tail waits for the two neighbours' flags only and leaves
-  // the dt MIN to the next step's first workgroup (lean_tile_body) or to
-  // hf2d_p2p_complete
-  int defer;
-  // cost attribution of the fused exchange (HF2D_FX_SKIP, timing only, wrong
-  // results): bit 0 no tail, bit 1 no edge pushes / mailbox stores, bit 2
-  // ghosts staged from the state arrays instead of the mailbox (no ghost
-  // prologue), bit 3 no loads of the push kernel
-  int skip;
-  int edge_first;   // inviscid fused tile kernel: edge tile columns dispatched first (HF2D_FX_EDGE_FIRST)
-  // tail completion count: one per dt shard + one for the shards, or one
-  // counter where the caller asks for it (fused lean N-S kernel, grids of <=
-  // FX_COUNT1_MAX workgroups); HF2D_FX_COUNT1 = 1 / 2 forces one / two levels.
-  // Loopback tail trace: the resonator's 4-rank strip (420 workgroups that
-  // finish spread out) 0.96 -> 0.52 us of counting and 4.4 -> 3.4 us of
-  // exchange with one counter; workgroups that finish together contend on it:
-  // the headline's 8-rank strip (719 single-wave workgroups) 5.5 -> 11.7 us,
-  // the scramjet's push kernel (135) 1.5 - 1.7 us of counting
-  int count1;
-};
-
-// Peer waits and publications are spread over the lanes of one wavefront:
-// lane q polls / publishes to peer q (q < nranks <= 64 per pass), so a step
-// costs one round trip to the fine-grained mailbox per phase instead of one
-// per peer (the single-thread loops cost ~12 us per step on an 8-rank strip,
-// tools/exchange_loopback.py, profiles/exchange_loopback_r05.md).
-__device__ inline double wave_min(double v) {
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) v = fmin(v, __shfl_xor(v, off, WAVE));
-  return v;
-}
-// Every lane of the calling wavefront: wait (bounded) for the flags of the
-// peers q with need(q) to reach target (acquire), and return the MIN of
-// their dt of parity par (fold) -- or 1.0 without fold.  False through *ok
-// after a timeout (neg_T bit 2) or an earlier one.
-template <class Need>
-__device__ inline double p2p_wait_wave(const FusedX& x, unsigned long long target, DevScalars* sc, Need need,
-                                       bool fold, int par, bool* ok) {
-  const int lane = (int)(threadIdx.x & (WAVE - 1));
-  bool good = !(__hip_atomic_load(&sc->neg_T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2);
-  double d = 1.0;
-  for (int q = lane; q < x.nranks && good; q += WAVE) {
-    if (q == x.rank || !need(q)) continue;
-    long spins = 0;
-    while (__hip_atomic_load(&x.my_flags[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < target) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > P2P_SPIN_LIMIT) {
-        atomicOr(&sc->neg_T, 2);
-        good = false;
-        break;
-      }
-    }
-    // acquire the peer's publication: its dt and mailbox stores (released by
-    // its vmcnt drain before the flag) are visible to every load ordered
-    // after this one, here and in later kernels
-    if (good) (void)p2p_acquire(&x.my_flags[q]);
-    if (good && fold) d = fmin(d, p2p_load(x.my_dtr + par * x.nranks + q));
-  }
-  *ok = __ballot(!good) == 0;
-  return wave_min(d);
-}
-__device__ inline bool p2p_wait_all(const FusedX& x, unsigned long long target, DevScalars* sc) {
-  bool ok;
-  (void)p2p_wait_wave(x, target, sc, [](int) { return true; }, false, 0, &ok);
-  return ok;
-}
-
-// Tail of a step kernel with the exchange fused in (wavefront 0 of every
-// workgroup, after the workgroup's mailbox stores and dt MIN): the last
-// workgroup to finish publishes this rank's step (its dt to every peer, then
-// flag seq_prev + 1), waits (bounded) for every peer's flag of the same step
-// -- the two neighbours' only with X.defer -- and folds their dt into the
-// slot the next step reads.
-// Returns true (every lane) in the last workgroup, after the wait.
-__device__ __forceinline__ bool fx_tail(const FusedX& X, DevScalars* sc, int slot_next,
-                                        unsigned long long seq_prev, bool fold = true, bool one_level = false) {
-  const int lane = (int)(threadIdx.x & (WAVE - 1));
-  const bool trace = (X.skip & 16) != 0;
-  unsigned long long c[FX_TRACE_W] = {};
-  if (trace) c[0] = rt_clock();
-  // the workgroup barrier drained every wave's mailbox stores; drain lane
-  // 0's dt atomic before counting this workgroup as done
-  vm_drain();
-  if (trace) c[1] = rt_clock();
-  // completion count in two levels (one counter per dt shard, then one for
-  // the shards): a single counter serialises every workgroup's returning
-  // atomic at the memory side
-  int last = 0;
-  if (lane == 0 && (X.count1 == 1 || (X.count1 == 0 && one_level))) {
-    unsigned* ct = X.done + DT_SHARDS * FX_DONE_STRIDE;
-    if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-      __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = 1;
-    }
-  } else if (lane == 0) {
-    const unsigned G = gridDim.x, sh = blockIdx.x % DT_SHARDS;
-    const unsigned pop = (G - sh + DT_SHARDS - 1) / DT_SHARDS, nsh = G < DT_SHARDS ? G : DT_SHARDS;
-    unsigned* cs = X.done + sh * FX_DONE_STRIDE;
-    unsigned* ct = X.done + DT_SHARDS * FX_DONE_STRIDE;
-    if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == pop - 1) {
-      __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsh - 1) {
-        __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = 1;
-      }
-    }
-  }
-  if (!__shfl(last, 0, WAVE)) return false;
-  if (trace) c[2] = rt_clock();
-  // last workgroup: this rank's dt (word + shards, one per lane), published
-  // to every peer (one peer per lane), then the flags, then the peers'
-  const unsigned long long sn = seq_prev + 1;
-  const int pn = (int)(sn & 1);
-  unsigned long long b = ~0ull;
-  if (lane < DT_SHARDS)
-    b = __hip_atomic_load(&sc->dt_sh[slot_next][lane][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (lane == DT_SHARDS) b = __hip_atomic_load(&sc->dt_bits[slot_next], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  double d = wave_min(b == ~0ull ? 1.0 : bits_to_d(b));
-  if (trace) c[3] = rt_clock();
-  for (int q = lane; q < X.nranks; q += WAVE)
-    if (q != X.rank) p2p_store(X.peer_dtr[q] + pn * X.nranks + X.rank, d);
-  vm_drain();   // (the wavefront's stores: every lane's)
-  if (trace) c[4] = rt_clock();
-  for (int q = lane; q < X.nranks; q += WAVE)
-    if (q != X.rank) __hip_atomic_store(&X.peer_flags[q][X.rank], sn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (trace) c[5] = rt_clock();
-  const bool defer = X.defer != 0;
-  const int r = X.rank;
-  bool ok;
-  const double peers = p2p_wait_wave(X, sn, sc, [=](int q) { return !defer || q == r - 1 || q == r + 1; },
-                                     fold && !defer, pn, &ok);
-  d = fmin(d, peers);
-  if (trace) c[6] = rt_clock();
-  if (lane == 0) {
-    if (fold && !defer && ok)
-      __hip_atomic_store(&sc->dt_bits[slot_next], d_to_bits(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *X.seq = sn;
-    if (trace) {
-      vm_drain();
-      c[7] = rt_clock();
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(X.done + (DT_SHARDS + 1) * FX_DONE_STRIDE) +
-                              (long)(sn % FX_TRACE_N) * FX_TRACE_W;
-#pragma unroll
-      for (int k = 0; k < FX_TRACE_W; k++) o[k] = c[k];
-    }
-  }
-  return true;
-}
-
-
-// Single-GPU last step of a host call (StepParams::host_sc): the last
-// workgroup to finish copies the slot's dt (word + shards) and the error flag
-// into the pinned host mirror (workgroup 0's head wrote time_part / dt_lag
-// there), so DeviceSolver::sync_scalars only waits for the stream: no
-// hf2d_scalars_out launch and its completion round trip (13 us of an idle
-// step(0) call, tools/call_overhead.py).  Completion count as fx_tail.
-__device__ __forceinline__ void host_mirror_tail(const StepParams& P, DevScalars* sc, int slot_next) {
-  const int lane = (int)(threadIdx.x & (WAVE - 1));
-  vm_drain();   // lane 0's dt atomic
-  int last = 0;
-  if (lane == 0) {
-    const unsigned G = gridDim.x, sh = blockIdx.x % DT_SHARDS;
-    const unsigned pop = (G - sh + DT_SHARDS - 1) / DT_SHARDS, nsh = G < DT_SHARDS ? G : DT_SHARDS;
-    unsigned* cs = P.host_done + sh * FX_DONE_STRIDE;
-    unsigned* ct = P.host_done + DT_SHARDS * FX_DONE_STRIDE;
-    if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == pop - 1) {
-      __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsh - 1) {
-        __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = 1;
-      }
-    }
-  }
-  if (!__shfl(last, 0, WAVE)) return;
-  unsigned long long b = ~0ull;
-  if (lane < DT_SHARDS) b = __hip_atomic_load(&sc->dt_sh[slot_next][lane][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (lane == DT_SHARDS) b = __hip_atomic_load(&sc->dt_bits[slot_next], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (P.dt_fold) {
-    // the step's MIN into the slot's word: the next step reads one word
-    // (StepParams::dt_read = 2) instead of the word and 16 shards
-    unsigned long long m = b;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) m = dt_bits_min(m, (unsigned long long)__shfl_xor((long long)m, off, WAVE));
-    m = (unsigned long long)__shfl((long long)m, 0, WAVE);
-    if (lane == DT_SHARDS) {
-      b = m;
-      __hip_atomic_store(&sc->dt_bits[slot_next], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (!P.host_sc) return;
-  DevScalars* h = static_cast<DevScalars*>(P.host_sc);
-  if (lane <= DT_SHARDS) (lane < DT_SHARDS ? h->dt_sh[slot_next][lane][0] : h->dt_bits[slot_next]) = b;
-  if (lane == DT_SHARDS + 1) h->neg_T = __hip_atomic_load(&sc->neg_T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// (workgroup 0's head, thread 0, after its updates of the slot words)
-__device__ __forceinline__ void host_mirror_head(const StepParams& P, const DevScalars* sc, int slot_next) {
-  DevScalars* h = static_cast<DevScalars*>(P.host_sc);
-  h->time_part = sc->time_part;
-  h->dt_lag[slot_next] = sc->dt_lag[slot_next];
-}
-
-// LDS-tiled lean step (lean_euler.hpp: lean_tile_stage / TileIO).
-// In-kernel phase trace (TR): thread 0 of every workgroup records the
-// 100 MHz s_memrealtime clock at entry, after the LDS staging barrier, when
-// its own wave finished computing, after the block dt reduction barrier and
-// after the dt atomic, plus the HW_ID / XCC_ID registers (DeviceSolver::trace_tile).
-constexpr int TILE_TRACE_WORDS = 8;
-#ifndef HF2D_TILE_STAGGER
-#define HF2D_TILE_STAGGER 1
-#endif
-constexpr int LDS_PER_CU = 160 * 1024;
-
-// part: 0 every tile; 1 the tiles of the strip's first and last tile column
-// (their results feed the halo exchange); 2 the other tiles.  The grid of a
-// part launch has exactly that many workgroups (DeviceSolver comm overlap).
-__device__ inline unsigned tile_of_part(unsigned bl, int part, const LeanTile& T) {
-  if (part == 1) return bl < (unsigned)T.nbj ? bl : (unsigned)((T.nbi - T.ne) * T.nbj) + (bl - T.nbj);
-  if (part == 2) return (unsigned)T.nbj + bl;
-  return bl;
-}
-
-// all tiles, the strip's edge tile columns first (the first one, then the
-// last T.ne), then the interior ones in order
-__device__ inline unsigned tile_edge_first(unsigned bl, const LeanTile& T) {
-  const unsigned nbj = (unsigned)T.nbj, ne = (unsigned)T.ne, nbi = (unsigned)T.nbi;
-  if (nbi < 2 + ne || bl < nbj) return bl;
-  if (bl < (1 + ne) * nbj) return (nbi - ne) * nbj + (bl - nbj);
-  return nbj + (bl - (1 + ne) * nbj);
-}
-
-// NT: threads per workgroup (BLOCK, or 128 / 64 for the small strips of a
-// multi-GPU run: at 250 x 200 cells per GPU a 256-thread tiling leaves ~50 of
-// the 256 CUs without a workgroup, and the step is one workgroup's
-// load -> compute -> reduce chain)
-template <bool RES, bool OUT, bool SG, int CPT, bool FX = false, bool TR = false, int NT = BLOCK>
-__device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, const LeanTile& T, DevScalars* sc,
-                                               int slot, int slot_next, int serial, ResidualPack* partials,
-                                               const FusedX& X = FusedX{}, unsigned long long* trace = nullptr,
-                                               int part = 0) {
-  extern __shared__ real lds[];
-  unsigned long long tr[5];
-  if (TR) tr[0] = rt_clock();
-  // (compiled into the single-gas two-cell kernel only: the mere presence of
-  // this block made the multi-gas one-cell kernel 3x slower on the triple
-  // point, 340 -> 1030 us, even with stagger 0)
-  if (HF2D_TILE_STAGGER && SG && CPT == 2 && !FX && NT == BLOCK && P.stagger != 0) {
-    // staggered start: every workgroup of a step is resident at once, so
-    // without it they all stage together (HBM saturated, VALUs idle) and
-    // then all compute (HBM idle); later dispatch rounds start loading while
-    // the earlier ones compute
-    // (rounds beyond the 4th are dispatched as earlier workgroups retire:
-    // no wait for them)
-    // (stagger > 0: whole rounds of stagger_wgs workgroups; < 0: a linear
-    // ramp of the same slope over the first four rounds)
-    const unsigned r = blockIdx.x / (unsigned)P.stagger_wgs;
-    if (r < 4 && (P.stagger < 0 || r > 0)) {
-      const unsigned long long d = P.stagger > 0 ? (unsigned long long)r * (unsigned)P.stagger
-                                                 : (unsigned long long)blockIdx.x * (unsigned)(-P.stagger) /
-                                                       (unsigned)P.stagger_wgs;
-      const unsigned long long t0 = rt_clock();
-      while (rt_clock() - t0 < d) __builtin_amdgcn_s_sleep(2);
-    }
-  }
-  // (fused exchange: the strip's edge tile columns first -- they push the
-  // halo and stage the ghost columns from the mailbox)
-  const unsigned b = (FX && X.edge_first) ? tile_edge_first(xcd_remap(blockIdx.x, gridDim.x), T)
-                                          : tile_of_part(xcd_remap(blockIdx.x, gridDim.x), part, T);
-  unsigned long long seq_prev = 0;
-  if (FX) seq_prev = *X.seq;
-  apply_dt(P, sc, slot, true);
-  if (b == 0 && threadIdx.x < WAVE) {
-    // lagged dt with the fold deferred (X.defer): the previous step's tail
-    // waited for the two neighbours only; the other ranks' dt of that step
-    // is folded here, one step later, by this wavefront (one peer per lane)
-    double fold = 1.0;
-    if (FX && X.defer && P.lag_dt && seq_prev > 0) {
-      bool ok;
-      fold = p2p_wait_wave(X, seq_prev, sc, [](int) { return true; }, true, (int)(seq_prev & 1), &ok);
-    }
-    if (threadIdx.x == 0) {
-      dt_reset(sc, slot_reset(slot));
-      lag_head(P, sc, slot, slot_next, fold);
-      sc->dt_bits[slot] = d_to_bits(P.dt);   // folded (later kernels of the step read the word)
-      sc->time_part += P.dt;
-      scenario_next(P, sc, slot, slot_next);
-      if (OUT && !RES && !FX && P.host_sc) host_mirror_head(P, sc, slot_next);
-    }
-  }
-  int i[CPT], j[CPT], c[CPT], i0, j0;
-  bool mine[CPT];
-  // own-cell global inputs first, so they are in flight during the staging
-  LeanOwn own[CPT];
-#pragma unroll
-  for (int q = 0; q < CPT; q++) {
-    mine[q] = lean_tile_cell(P, T, (int)b, (int)threadIdx.x, &i[q], &j[q], &c[q], &i0, &j0, q);
-    if (mine[q]) lean_load_own<TileIO<SG>::NE>(L, (long)i[q] * P.ny + j[q], own[q]);
-  }
-  if (!FX || seq_prev == 0 || (X.skip & 4) || (i0 - 1 > P.i0 - 1 && i0 + T.TI < P.i1)) {
-    lean_tile_stage<SG>(P, L, T, i0, j0, lds, threadIdx.x, NT);
-  } else {
-    // edge tile: the ghost column comes from the mailbox of parity seq_prev
-    constexpr int NF = SG ? LEAN_TILE_FIELDS_SG : LEAN_TILE_FIELDS;
-    const int pp = (int)(seq_prev & 1);
-    const real* mbL = X.my_recv + ((long)pp * 2) * X.cap;
-    const real* mbR = X.my_recv + ((long)pp * 2 + 1) * X.cap;
-    const long N = L.N;
-    constexpr int NS = SG ? 4 : 4 + NCOMP;
-    constexpr int FU = SG ? 4 : 10;
-    for (int c = threadIdx.x; c < T.NC; c += NT) {
-      const int ii = c / T.W - 1, jj = c - (ii + 1) * T.W - 1;
-      const bool xh = ii < 0 || ii >= T.TI, yh = jj < 0 || jj >= T.TJ;
-      const int gi = i0 + ii, gj = j0 + jj;
-      if ((xh && yh) || gi < 0 || gi >= P.nx || gj < 0 || gj >= P.ny) continue;
-      const bool gl = (X.sides & 1) && gi == P.i0 - 1, gr = (X.sides & 2) && gi == P.i1;
-      if (gl || gr) {
-        const real* mb = gl ? mbL : mbR;
-#pragma unroll
-        for (int f = 0; f < NF; f++) lds[f * T.NC + c] = p2p_load(mb + (long)f * P.ny + gj);
-        continue;
-      }
-      const long g = (long)gi * P.ny + gj;
-#pragma unroll
-      for (int f = 0; f < NS; f++) lds[f * T.NC + c] = L.Sin[f * N + g];
-      if (!SG)
-#pragma unroll
-        for (int f = 0; f < NCOMP; f++) lds[(4 + NCOMP + f) * T.NC + c] = L.Pin_s[f * N + g];
-      lds[FU * T.NC + c] = L.Uin[g];
-      lds[(FU + 1) * T.NC + c] = L.Vin[g];
-      lds[(FU + 2) * T.NC + c] = L.Pin[g];
-    }
-  }
-  __syncthreads();
-  // (raising the wave priority here for the compute phase, s_setprio 2,
-  // measured no change: headline 26.9 - 27.2 us either way, triple point
-  // 350 - 353 us)
-  if (TR) tr[1] = rt_clock();
-  ResidualPack r;
-  if (RES) {
-    residual_reset(r);
-#pragma unroll
-    for (int k = 0; k < NEQ; k++) r.eq[k].i = r.eq[k].j = -1;
-  }
-  double dtl = 1.0;
-  int neg = 0;
-#pragma unroll
-  for (int q = 0; q < CPT; q++) {
-    if (mine[q]) {
-      TileIO<SG> io(L, (long)i[q] * P.ny + j[q], lds, T.NC, T.W, c[q]);
-      dtl = fmin(dtl, lean_cell<RES, OUT>(P, L, io, own[q], i[q], j[q], r, &neg));
-      if (FX) {
-        const bool pl = (X.sides & 1) && i[q] == P.i0, pr = (X.sides & 2) && i[q] == P.i1 - 1;
-        if ((pl || pr) && !(X.skip & 2)) {   // new lean state of an edge cell -> the neighbour's mailbox of parity seq_prev + 1
-          constexpr int NF = SG ? LEAN_TILE_FIELDS_SG : LEAN_TILE_FIELDS;
-          constexpr int NS = SG ? 4 : 4 + NCOMP;
-          const int pn = (int)((seq_prev + 1) & 1);
-          real* mb = pl ? X.peer_recv_l + ((long)pn * 2 + 1) * X.cap : X.peer_recv_r + ((long)pn * 2) * X.cap;
-          const long N = L.N, g = (long)i[q] * P.ny + j[q];
-          real v[NF];
-#pragma unroll
-          for (int f = 0; f < NS; f++) v[f] = L.Sout[f * N + g];
-          if (!SG)
-#pragma unroll
-            for (int f = 0; f < NCOMP; f++) v[4 + NCOMP + f] = L.Pout_s[f * N + g];
-          v[NF - 3] = L.Uout[g];
-          v[NF - 2] = L.Vout[g];
-          v[NF - 1] = L.Pout[g];
-#pragma unroll
-          for (int f = 0; f < NF; f++) p2p_store(mb + (long)f * P.ny + j[q], v[f]);
-          vm_drain();
-        }
-      }
-    }
-  }
-  if (TR) tr[2] = rt_clock();
-  if (RES) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)b * (NT / WAVE) + threadIdx.x / WAVE] = r;
-  }
-  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
-  __shared__ double sdt[NT / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
-  if (neg) {
-    atomicOr(&sc->neg_T, 1);
-    if (OUT && !RES && !FX && P.host_sc) vm_drain();   // (done before host_mirror_tail's count)
-  }
-  __syncthreads();
-  if (TR) tr[3] = rt_clock();
-  if (threadIdx.x == 0) {
-    double m = sdt[0];
-    for (int q = 1; q < NT / WAVE; q++) m = fmin(m, sdt[q]);
-    if (serial) m = fmin(m, P.dt);
-    dt_min(sc, slot_next, m);
-    if (TR) {
-      vm_drain();
-      tr[4] = rt_clock();
-      unsigned long long* o = trace + (long)b * TILE_TRACE_WORDS;
-#pragma unroll
-      for (int q = 0; q < 5; q++) o[q] = tr[q];
-      o[5] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_ID: wave/SIMD/CU/SE
-      o[6] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20);   // XCC_ID
-      o[7] = blockIdx.x;
-    }
-  }
-  if (FX && threadIdx.x < WAVE && !(X.skip & 1)) fx_tail(X, sc, slot_next, seq_prev);
-  if (!FX && !TR && (P.dt_fold || (OUT && !RES && P.host_sc)) && threadIdx.x < WAVE)
-    host_mirror_tail(P, sc, slot_next);
-}
-
-// No occupancy attribute on the default kernel: the backend's own register
-// budget (94 VGPRs here) beat every explicit amdgpu_waves_per_eu we tried.
-template <bool RES, bool OUT, bool SG, int OCC = 0, int CPT = 1>
-__global__ __launch_bounds__(BLOCK) void hf2d_lean_tile(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc,
-                                                         int slot, int slot_next, int serial,
-                                                         ResidualPack* partials, int part = 0) {
-  lean_tile_body<RES, OUT, SG, CPT>(P, L, T, sc, slot, slot_next, serial, partials, FusedX{}, nullptr, part);
-}
-
-// Phase-traced plain step (profiling only, DeviceSolver::trace_tile).
-template <bool SG, int CPT>
-__global__ __launch_bounds__(BLOCK) void hf2d_lean_tile_tr(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc,
-                                                            int slot, int slot_next, int serial,
-                                                            ResidualPack* partials, unsigned long long* trace) {
-  lean_tile_body<false, false, SG, CPT, false, true>(P, L, T, sc, slot, slot_next, serial, partials, FusedX{}, trace);
-}
-
-// Same step with the multi-GPU exchange fused in (FusedX).
-template <bool RES, bool OUT, bool SG, int CPT>
-// (the exchange arguments by pointer, read where they are used: by value
-// they took ~26 SGPRs of the kernel arguments, and the 64-thread fused
-// kernel spilled 96 SGPRs to VGPR lanes against 28 for the plain one)
-__global__ __launch_bounds__(BLOCK) void hf2d_lean_tile_fx(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc,
-                                                            int slot, int slot_next, int serial,
-                                                            ResidualPack* partials, const FusedX* __restrict__ X) {
-  lean_tile_body<RES, OUT, SG, CPT, true>(P, L, T, sc, slot, slot_next, serial, partials, *X);
-}
-
-// Small-strip geometries (single gas): NT = 128 / 64 threads per workgroup
-// (picked by the ThreadBlockSize = 0 autotune per strip)
-template <bool RES, bool OUT, int NT, int CPT>
-__global__ __launch_bounds__(NT) void hf2d_lean_tile_nt(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc,
-                                                       int slot, int slot_next, int serial, ResidualPack* partials,
-                                                       int part = 0) {
-  lean_tile_body<RES, OUT, true, CPT, false, false, NT>(P, L, T, sc, slot, slot_next, serial, partials, FusedX{},
-                                                        nullptr, part);
-}
-template <bool RES, bool OUT, int NT, int CPT>
-__global__ __launch_bounds__(NT) void hf2d_lean_tile_fx_nt(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc,
-                                                          int slot, int slot_next, int serial,
-                                                          ResidualPack* partials, const FusedX* __restrict__ X) {
-  lean_tile_body<RES, OUT, true, CPT, true, false, NT>(P, L, T, sc, slot, slot_next, serial, partials, *X);
-}
-template <int NT, int CPT>
-__global__ __launch_bounds__(NT) void hf2d_lean_tile_tr_nt(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc,
-                                                          int slot, int slot_next, int serial,
-                                                          ResidualPack* partials, unsigned long long* trace) {
-  lean_tile_body<false, false, true, CPT, false, true, NT>(P, L, T, sc, slot, slot_next, serial, partials, FusedX{},
-                                                           trace);
-}
-
-// Ghost columns + global dt after fused steps, for any other consumer: wait
-// for the peers' last publication, copy the mailbox of that parity into the
-// ghost columns of the current state, fold the dt MIN into the slot.
-__global__ __launch_bounds__(P2P_THREADS) void hf2d_p2p_complete(ColList Lc, int ghostL, int ghostR, int ny, int cnt,
-                                                                 FusedX X, DevScalars* sc, int dslot) {
-  const unsigned long long sq = *X.seq;
-  if (sq == 0) return;
-  __shared__ int ok;
-  if (threadIdx.x < WAVE) {
-    const bool w = p2p_wait_all(X, sq, sc);
-    if (threadIdx.x == 0) ok = w ? 1 : 0;
-  }
-  __syncthreads();
-  if (!ok) return;
-  const int pp = (int)(sq & 1);
-  if (X.sides & 1) {
-    const real* src = X.my_recv + ((long)pp * 2) * X.cap;
-    for (int t = threadIdx.x; t < cnt; t += P2P_THREADS) {
-      const int f = t / ny, j = t - f * ny;
-      Lc.f[f][(long)ghostL * ny + j] = p2p_load(src + t);
-    }
-  }
-  if (X.sides & 2) {
-    const real* src = X.my_recv + ((long)pp * 2 + 1) * X.cap;
-    for (int t = threadIdx.x; t < cnt; t += P2P_THREADS) {
-      const int f = t / ny, j = t - f * ny;
-      Lc.f[f][(long)ghostR * ny + j] = p2p_load(src + t);
-    }
-  }
-  if (threadIdx.x == 0) {
-    double m = dt_get(sc, dslot);
-    for (int q = 0; q < X.nranks; q++)
-      if (q != X.rank) m = fmin(m, p2p_load(X.my_dtr + pp * X.nranks + q));
-    sc->dt_bits[dslot] = d_to_bits(m);
-  }
-}
-
-template <bool RES, bool OUT, bool SG, int OCC, int CPT = 1>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(OCC)))
-void hf2d_lean_tile_occ(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc, int slot, int slot_next, int serial,
-                        ResidualPack* partials) {
-  lean_tile_body<RES, OUT, SG, CPT>(P, L, T, sc, slot, slot_next, serial, partials);
 }
 
 // K8 monitors: p and Tg of the probe cells this rank owns (idx < 0: not
@@ -1230,73 +612,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(3))) void
   lns_step_body<RES, MODE, TURB, true>(P, a, T, sc, slot, slot_next, serial, partials, 0, X, &Lc, Lg);
 }
 
-// Multi-workgroup mailbox exchange, push half (the mechanism step and every
-// other p2p exchange with p2p_fuse): each thread loads up to PER boundary
-// values of the fields in Lc (column first + o / last - o) and stores them
-// into the neighbours' mailboxes; the last workgroup publishes and, fold,
-// folds the peers' dt into dslot (fx_tail); hf2d_p2p_unpack follows.
-// publish = 0: the pushes only (drained); a later hf2d_p2p_finish publishes
-// the step -- the mechanism step pushes its edge tiles' halo before its
-// interior tiles run.
-template <int PER>
-__global__ __launch_bounds__(BLOCK) void hf2d_p2p_push(ColList Lc, int first, int last, int ny, int cnt, FusedX X,
-                                                      DevScalars* sc, int dslot, int fold, int publish) {
-  const unsigned long long seq_prev = *X.seq;
-  const int pn = (int)((seq_prev + 1) & 1);
-  // value u of a thread: base + u * BLOCK (consecutive lanes, consecutive
-  // addresses: with PER consecutive values per thread every load and mailbox
-  // store instruction touched 64 different lines)
-  const long base = (long)blockIdx.x * BLOCK * PER + threadIdx.x;
-  real v[PER];
-#pragma unroll
-  for (int u = 0; u < PER; u++) {
-    const long t = base + (long)u * BLOCK;
-    if (t < 2L * cnt) {
-      const int side = t < cnt ? 0 : 1;
-      const int tt = (int)(t - (long)side * cnt), f = tt / ny, j = tt - f * ny;
-      if ((X.sides & (1 << side)) && !(X.skip & 8))
-        v[u] = Lc.f[f][(long)(side == 0 ? first + Lc.o[f] : last - Lc.o[f]) * ny + j];
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < PER; u++) {
-    const long t = base + (long)u * BLOCK;
-    if (t < 2L * cnt) {
-      const int side = t < cnt ? 0 : 1;
-      const int tt = (int)(t - (long)side * cnt);
-      // the left neighbour receives "from right", the right one "from left"
-      if ((X.sides & (1 << side)) && !(X.skip & 2))
-        p2p_store((side == 0 ? X.peer_recv_l + ((long)pn * 2 + 1) * X.cap : X.peer_recv_r + ((long)pn * 2) * X.cap) +
-                      tt,
-                  v[u]);
-    }
-  }
-  vm_drain();
-  if (!publish) return;
-  __syncthreads();
-  if (threadIdx.x < WAVE && !(X.skip & 1)) fx_tail(X, sc, dslot, seq_prev, fold != 0);
-}
-
-using PushK = void (*)(ColList, int, int, int, int, FusedX, DevScalars*, int, int, int);
-// values per thread of the push kernel (HF2D_PUSH_PER: 1, 4 or 16) and its
-// grid: one value per thread (135 workgroups on the scramjet's 8-rank strip)
-// pushed the 43-field mechanism halo in 7.0 us against 15.4 us with 16 values
-// per thread on 9 workgroups (rocprofv3 kernel trace of tools/exchange_loopback.py;
-// loopback exchange 18.7 -> 8.2 us)
-inline PushK push_kernel(int per) {
-  return per == 16 ? hf2d_p2p_push<16> : per == 4 ? hf2d_p2p_push<4> : hf2d_p2p_push<1>;
-}
-inline unsigned push_grid(int per, int cnt) {
-  const int p = per == 16 || per == 4 ? per : 1;
-  return (unsigned)std::max(1, (2 * cnt + BLOCK * p - 1) / (BLOCK * p));
-}
-
-// One workgroup: publish the step whose halo an earlier hf2d_p2p_push
-// (publish = 0) stored, wait for the peers' publication, fold their dt.
-__global__ void hf2d_p2p_finish(FusedX X, DevScalars* sc, int dslot) {
-  fx_tail(X, sc, dslot, *X.seq, true);   // (one wavefront)
-}
-
 // The scalars the host reads (the words before the dt shards, and the shards
 // of the dt slot it reads) into pinned host memory with plain vector stores,
 // queued behind the step's kernels: the host then waits for the stream only,
@@ -1312,21 +627,6 @@ __global__ __launch_bounds__(WAVE) void hf2d_scalars_out(const DevScalars* sc, D
   if (t < DT_SHARDS) host->dt_sh[slot][t][0] = sc->dt_sh[slot][t][0];
 }
 
-// Ghost columns of the HALO_LNS group from the mailbox of the step the fused
-// tail just completed (it waited for every peer's flag): entry f of side s
-// goes to ghost column ghostL - o[f] / ghostR + o[f] (grid-stride, one value
-// per thread).
-__global__ __launch_bounds__(BLOCK) void hf2d_p2p_unpack(ColList Lc, int ghostL, int ghostR, int ny, int cnt,
-                                                        FusedX X) {
-  const int par = (int)(*X.seq & 1);
-  for (long t = (long)blockIdx.x * BLOCK + threadIdx.x; t < 2L * cnt; t += (long)gridDim.x * BLOCK) {
-    const int side = t < cnt ? 0 : 1;
-    if (!(X.sides & (1 << side))) continue;
-    const int tt = (int)(t - (long)side * cnt), f = tt / ny, j = tt - f * ny;
-    const real v = p2p_load(X.my_recv + ((long)par * 2 + side) * X.cap + tt);
-    Lc.f[f][(long)(side == 0 ? ghostL - Lc.o[f] : ghostR + Lc.o[f]) * ny + j] = v;
-  }
-}
 // register budget of OCC waves per SIMD (DeviceSolver::lns_occ, measured)
 template <bool RES, int MODE, int OCC, int TURB = 2>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(OCC))) void hf2d_lns_step_occ(
@@ -1727,210 +1027,6 @@ __global__ __launch_bounds__(BLOCK) void hf2d_yplus(SoA s, long c0, long c1, con
   y_plus_apply(s, c, uw, ok);
 }
 
-
-__global__ void hf2d_pack(ColList L, int col, int ny, real* buf) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= L.nf * ny) return;
-  const int f = t / ny, j = t - f * ny;
-  buf[t] = L.f[f][(long)col * ny + j];
-}
-__global__ void hf2d_unpack(ColList L, int col, int ny, const real* buf) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= L.nf * ny) return;
-  const int f = t / ny, j = t - f * ny;
-  L.f[f][(long)col * ny + j] = buf[t];
-}
-// Both sides in one launch (sides: bit 0 left, bit 1 right).
-// dt slot's shards into its word (before a host transport sends the word)
-__global__ void hf2d_dt_commit(DevScalars* sc, int slot) {
-  if (threadIdx.x == 0) sc->dt_bits[slot] = d_to_bits(dt_get(sc, slot));
-}
-// MIN of the peers' dt into this rank's slot (exchange_dt, in-process group)
-__global__ void hf2d_fold_dt(DevScalars* sc, int slot, const double* dt_recv, int nranks, int rank) {
-  if (threadIdx.x != 0) return;
-  double m = dt_get(sc, slot);
-  for (int q = 0; q < nranks; q++)
-    if (q != rank) m = fmin(m, dt_recv[q]);
-  sc->dt_bits[slot] = d_to_bits(m);
-}
-
-// (dslot >= 0: also commits that dt slot's shards into its word, which the
-// host transports send)
-__global__ void hf2d_pack2(ColList L, int colL, int colR, int ny, real* bufL, real* bufR, int sides,
-                           DevScalars* sc, int dslot) {
-  const int cnt = L.nf * ny;
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0 && dslot >= 0) sc->dt_bits[dslot] = d_to_bits(dt_get(sc, dslot));
-  const bool right = t >= cnt;
-  if (right) t -= cnt;
-  if (t >= cnt || !(sides & (right ? 2 : 1))) return;
-  const int f = t / ny, j = t - f * ny;
-  (right ? bufR : bufL)[t] = L.f[f][(long)(right ? colR - L.o[f] : colL + L.o[f]) * ny + j];
-}
-// Also folds the dt gathered from the other ranks (ndt > 0: dtr[q], q != self)
-// into the next dt slot: MIN of positive doubles, exact in any order.
-__global__ void hf2d_unpack2(ColList L, int colL, int colR, int ny, const real* bufL, const real* bufR,
-                             int sides, DevScalars* sc, int dslot, const double* dtr, int ndt, int self) {
-  const int cnt = L.nf * ny;
-  int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0 && ndt > 0) {
-    double m = dt_get(sc, dslot);
-    for (int q = 0; q < ndt; q++)
-      if (q != self) m = fmin(m, dtr[q]);
-    sc->dt_bits[dslot] = d_to_bits(m);
-  }
-  const bool right = t >= cnt;
-  if (right) t -= cnt;
-  if (t >= cnt || !(sides & (right ? 2 : 1))) return;
-  const int f = t / ny, j = t - f * ny;
-  L.f[f][(long)(right ? colR + L.o[f] : colL - L.o[f]) * ny + j] = (right ? bufR : bufL)[t];
-}
-
-// ---------------------------------------------------------------------------
-// xGMI peer-to-peer halo transport (default for multi-GPU strips).
-//
-// Every rank owns one fine-grained "mailbox" allocation, mapped into its
-// peers with IPC handles:
-//   flags[nranks]  u64   step sequence number last published by rank q
-//   dtr[2][nranks] f64   dt of rank q for sequence parity 0/1
-//   recv[2][2][cap] f64  halo columns for parity 0/1 from the left/right
-// One single-workgroup kernel per exchange replaces pack + RCCL group +
-// unpack: it stores this rank's boundary columns straight into the
-// neighbours' mailboxes and its dt into every peer's, publishes its flag,
-// waits (bounded) for every peer's flag of the same sequence number, then
-// unpacks its own mailbox into the ghost columns and folds the MIN of all dt
-// into the next dt slot -- bitwise the RCCL path's result.
-// Ordering without system-scope fences: mailbox data and flags are written
-// with system-coherent stores (p2p_store: they bypass the non-coherent L2),
-// and a wave's stores are complete (s_waitcnt vmcnt(0)) before any flag is
-// stored; a reader issues its system-coherent data loads only after it has
-// seen the flag.  A __threadfence_system() would also write back the whole
-// L2 of the XCD (buffer_wbl2), which cost ~3 us per step in the fused kernel.
-// Parity double buffering is safe without a second handshake: a peer writes
-// parity p again only at sequence s+2, after it has seen this rank's flag
-// s+1, which is published after the unpack of s.  The sequence counter lives
-// in device memory, so the kernel replays unchanged inside step graphs.
-// ---------------------------------------------------------------------------
-
-
-struct P2PArgs {
-  ColList L;
-  int first, last, ghostL, ghostR, ny, cnt, sides;
-  long cap;                              // doubles per (parity, side) mailbox slot
-  real* peer_recv_l;                     // left neighbour's recv base (this rank is its right side)
-  real* peer_recv_r;                     // right neighbour's recv base
-  real* my_recv;
-  unsigned long long* const* peer_flags; // [nranks] flag array of each rank (self: own)
-  double* const* peer_dtr;               // [nranks] dtr array of each rank
-  unsigned long long* my_flags;
-  double* my_dtr;
-  unsigned long long* seq;               // device-side sequence counter
-  DevScalars* sc;
-  int dslot, fold_dt, rank, nranks;
-};
-
-
-
-__global__ __launch_bounds__(P2P_THREADS) void hf2d_p2p_xchg(P2PArgs a) {
-  const unsigned long long seq = *a.seq + 1;
-  const int par = (int)(seq & 1);
-  const int ny = a.ny;
-  // 1. push boundary columns and this rank's dt into the peers' mailboxes:
-  // PER loads of a thread in flight, then its PER system-coherent stores (one
-  // load latency per batch instead of one per value: the N-S halo is 23-43
-  // fields x ny per side)
-  constexpr int PER = 16;
-  const int total = ((a.sides & 1) ? a.cnt : 0) + ((a.sides & 2) ? a.cnt : 0);
-  for (int base = 0; base < total; base += PER * P2P_THREADS) {
-    real v[PER];
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-      const int t = base + u * P2P_THREADS + threadIdx.x;
-      if (t < total) {
-        const bool right = !(a.sides & 1) || t >= a.cnt;
-        const int tt = (a.sides & 1) && right ? t - a.cnt : t;
-        const int f = tt / ny, j = tt - f * ny;
-        v[u] = a.L.f[f][(long)(right ? a.last - a.L.o[f] : a.first + a.L.o[f]) * ny + j];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-      const int t = base + u * P2P_THREADS + threadIdx.x;
-      if (t < total) {
-        const bool right = !(a.sides & 1) || t >= a.cnt;
-        const int tt = (a.sides & 1) && right ? t - a.cnt : t;
-        // the left neighbour receives "from right", the right one "from left"
-        real* dst = right ? a.peer_recv_r + ((long)par * 2) * a.cap : a.peer_recv_l + ((long)par * 2 + 1) * a.cap;
-        p2p_store(dst + tt, v[u]);
-      }
-    }
-  }
-  const double mydt = dt_get(a.sc, a.dslot);
-  for (int q = threadIdx.x; q < a.nranks; q += P2P_THREADS)
-    if (q != a.rank) p2p_store(a.peer_dtr[q] + par * a.nranks + a.rank, mydt);
-  // system-coherent stores drained (vmcnt) in every wave before the flag:
-  // no L2 writeback needed, nothing of this kernel sits dirty in the L2
-  vm_drain();
-  __syncthreads();
-  // 2. publish, 3. wait for every peer's publication of the same sequence
-  for (int q = threadIdx.x; q < a.nranks; q += P2P_THREADS)
-    if (q != a.rank) __hip_atomic_store(&a.peer_flags[q][a.rank], seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const bool failed = __hip_atomic_load(&a.sc->neg_T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2;
-  __shared__ double s_dt[P2P_THREADS];
-  double dmin = mydt;   // each polling thread folds the dt of the peers it waited for
-  for (int q = threadIdx.x; q < a.nranks; q += P2P_THREADS) {
-    if (q == a.rank || failed) continue;   // after one timeout, stop waiting (the host reports it)
-    long spins = 0;
-    bool ok = true;
-    while (__hip_atomic_load(&a.my_flags[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < seq) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++spins > P2P_SPIN_LIMIT) {
-        atomicOr(&a.sc->neg_T, 2);
-        ok = false;
-        break;
-      }
-    }
-    if (ok) (void)p2p_acquire(&a.my_flags[q]);   // order the mailbox reads after the flag
-    if (ok) dmin = fmin(dmin, p2p_load(a.my_dtr + par * a.nranks + q));
-  }
-  s_dt[threadIdx.x] = dmin;
-  __syncthreads();
-  // 4. unpack this rank's mailbox into the ghost columns: all loads of a
-  // thread first, then its stores (the stores may alias nothing the loads
-  // read, but the compiler cannot know that)
-  for (int base = 0; base < total; base += PER * P2P_THREADS) {
-    real v[PER];
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-      const int t = base + u * P2P_THREADS + threadIdx.x;
-      if (t < total) {
-        const bool right = !(a.sides & 1) || t >= a.cnt;
-        const int tt = (a.sides & 1) && right ? t - a.cnt : t;
-        v[u] = p2p_load(a.my_recv + ((long)par * 2 + (right ? 1 : 0)) * a.cap + tt);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-      const int t = base + u * P2P_THREADS + threadIdx.x;
-      if (t < total) {
-        const bool right = !(a.sides & 1) || t >= a.cnt;
-        const int tt = (a.sides & 1) && right ? t - a.cnt : t;
-        const int f = tt / ny, j = tt - f * ny;
-        a.L.f[f][(long)(right ? a.ghostR + a.L.o[f] : a.ghostL - a.L.o[f]) * ny + j] = v[u];
-      }
-    }
-  }
-  // 5. global dt: MIN over ranks (exact in any order)
-  if (threadIdx.x == 0) {
-    if (a.fold_dt) {
-      double m = mydt;
-      for (int q = 0; q < a.nranks && q < P2P_THREADS; q++) m = fmin(m, s_dt[q]);
-      a.sc->dt_bits[a.dslot] = d_to_bits(m);
-    }
-    *a.seq = seq;
-  }
-}
-
 // ---------------------------------------------------------------------------
 // DeviceSolver
 // ---------------------------------------------------------------------------
@@ -1993,6 +1089,17 @@ static const TileTrK kTileTrNt[2][2] = {{hf2d_lean_tile_tr_nt<128, 1>, hf2d_lean
                                         {hf2d_lean_tile_tr_nt<64, 1>, hf2d_lean_tile_tr_nt<64, 2>}};
 // threads per workgroup of the inviscid tile kernel: 256, or 128 / 64 (single gas)
 inline int tile_nt(int want, bool sg) { return sg && (want == 128 || want == 64) ? want : BLOCK; }
+// the kernel of a family for nt threads per workgroup (below 256: the
+// single-gas small-workgroup tables), cpt cells per thread and variant var
+inline TileK tile_kernel(int nt, bool sg, int cpt, int var) {
+  return nt == BLOCK ? kTile[sg][cpt - 1][var] : kTileNt[nt == 128 ? 0 : 1][cpt - 1][var];
+}
+inline TileFxK tile_fx_kernel(int nt, bool sg, int cpt, int var) {
+  return nt == BLOCK ? kTileFx[sg][cpt - 1][var] : kTileFxNt[nt == 128 ? 0 : 1][cpt - 1][var];
+}
+inline TileTrK tile_tr_kernel(int nt, bool sg, int cpt) {
+  return nt == BLOCK ? kTileTr[sg][cpt - 1] : kTileTrNt[nt == 128 ? 0 : 1][cpt - 1];
+}
 
 using LeanEulerK = void (*)(StepParams, LeanSoA, long, long, DevScalars*, int, int, int, ResidualPack*);
 // [residual][first lean step: from the generic arrays]
@@ -3579,57 +2686,63 @@ void DeviceSolver::halo_fields(int group, std::vector<real*>& f, bool full) cons
   halo_fields(group, f, o, full);
 }
 
-void DeviceSolver::halo_fields(int group, std::vector<real*>& f, std::vector<unsigned char>& o, bool full) const {
+// HALO_LNS: lean N-S / mechanism strips (two ghost columns): what the next
+// lean step reads of them -- the inner ghost column is a ring cell (its fill
+// reads its predicted state, lagged primitives, transport and thermodynamic
+// state), the outer one only the neighbour values of that fill (state,
+// species, lagged U, V, T).  For the buffer parities sb / pb / cb / ds (a
+// fused step lists its post-step buffers before it flips the members).
+void DeviceSolver::halo_fields_lns(std::vector<real*>& f, std::vector<unsigned char>& o, int sb, int pb, int cb,
+                                   int ds) const {
   const Impl& m = *impl;
   const long N = h.N;
   f.clear();
   o.clear();
-  if (group == CpuSolver::HALO_LNS) {
-    // lean N-S / mechanism strips (two ghost columns): what the next lean step
-    // reads of them -- the inner ghost column is a ring cell (its fill reads
-    // its predicted state, lagged primitives, transport and thermodynamic
-    // state), the outer one only the neighbour values of that fill (state,
-    // species, lagged U, V, T)
-    const int cb = cbuf;
-    auto two = [&](real* p) {
-      f.push_back(p);
-      o.push_back(0);
-      f.push_back(p);
-      o.push_back(1);
-    };
-    auto one = [&](real* p) {
-      f.push_back(p);
-      o.push_back(0);
-    };
-    for (int k = 0; k < NEQ; k++)
-      if (sk_live(m.mech ? SK_MECH : sk_mode, k)) two(m.S[1 - sbuf] + (long)k * N);
-    two(m.U[1 - pbuf]);
-    two(m.V[1 - pbuf]);
-    two(m.Tg[1 - pbuf]);
-    real* const mux[2] = {m.mu, m.mu2};
-    real* const lamx[2] = {m.lam, m.lam2};
-    real* const mutx[2] = {m.mu_t, m.mu_t2};
-    real* const cpx[2] = {m.CP, m.CP2};
-    real* const kkx[2] = {m.kk, m.kk2};
-    one(mux[1 - cb]);
-    one(lamx[1 - cb]);
-    one(mutx[1 - cb]);
-    one(cpx[1 - cb]);
-    one(kkx[1 - cb]);
-    if (m.mech) {
-      real* const px[2] = {m.p, m.p2};
-      one(px[1 - cb]);
-      one(m.Tst[1 - cb]);
-      for (int q = 0; q < m.nsp; q++) two(m.Ys[sbuf] + (long)q * N);
-    }
-    if (any_cauchy_x) {   // dS/dx of the ghost column (Cauchy neighbours of the edge cells)
-      for (int k = 0; k < NEQ; k++)
-        if (sk_live(m.mech ? SK_MECH : sk_mode, k)) one(m.dSdx[dsbuf] + (long)k * N);
-      if (m.dSdxs[0])
-        for (int q = 0; q < m.nsp; q++) one(m.dSdxs[dsbuf] + (long)q * N);
-    }
-    return;
+  auto two = [&](real* p) {
+    f.push_back(p);
+    o.push_back(0);
+    f.push_back(p);
+    o.push_back(1);
+  };
+  auto one = [&](real* p) {
+    f.push_back(p);
+    o.push_back(0);
+  };
+  for (int k = 0; k < NEQ; k++)
+    if (sk_live(m.mech ? SK_MECH : sk_mode, k)) two(m.S[1 - sb] + (long)k * N);
+  two(m.U[1 - pb]);
+  two(m.V[1 - pb]);
+  two(m.Tg[1 - pb]);
+  real* const mux[2] = {m.mu, m.mu2};
+  real* const lamx[2] = {m.lam, m.lam2};
+  real* const mutx[2] = {m.mu_t, m.mu_t2};
+  real* const cpx[2] = {m.CP, m.CP2};
+  real* const kkx[2] = {m.kk, m.kk2};
+  one(mux[1 - cb]);
+  one(lamx[1 - cb]);
+  one(mutx[1 - cb]);
+  one(cpx[1 - cb]);
+  one(kkx[1 - cb]);
+  if (m.mech) {
+    real* const px[2] = {m.p, m.p2};
+    one(px[1 - cb]);
+    one(m.Tst[1 - cb]);
+    for (int q = 0; q < m.nsp; q++) two(m.Ys[sb] + (long)q * N);
   }
+  if (any_cauchy_x) {   // dS/dx of the ghost column (Cauchy neighbours of the edge cells)
+    for (int k = 0; k < NEQ; k++)
+      if (sk_live(m.mech ? SK_MECH : sk_mode, k)) one(m.dSdx[ds] + (long)k * N);
+    if (m.dSdxs[0])
+      for (int q = 0; q < m.nsp; q++) one(m.dSdxs[ds] + (long)q * N);
+  }
+}
+
+void DeviceSolver::halo_fields(int group, std::vector<real*>& f, std::vector<unsigned char>& o, bool full) const {
+  if (group == CpuSolver::HALO_LNS) return halo_fields_lns(f, o, sbuf, pbuf, cbuf, dsbuf);
+  const Impl& m = *impl;
+  const long N = h.N;
+  f.clear();
+  o.clear();
   full = full || !halo_compact;
   const int mode = split_mode();
   auto add_eq = [&](real* base) {
@@ -4249,12 +3362,14 @@ void DeviceSolver::run_graph() {
 }
 
 // Split predict + fill step (every N-S / mechanism / generic case).
-void DeviceSolver::step_split(const StepParams& P0, bool want_res, int slot, int slot_next, int serial, unsigned nblk,
-                              bool to_lns) {
-  StepParams P = P0;
+DeviceSolver::StepDone DeviceSolver::step_split(const StepCtx& c, bool to_lns) {
+  StepParams P = c.P;
   Impl& m = *impl;
   hipStream_t st = m.stream;
-  const long c0 = (long)P.i0 * P.ny, c1 = (long)P.i1 * P.ny;
+  const bool want_res = c.want_res;
+  const int slot = c.slot, slot_next = c.slot_next, serial = c.serial;
+  const unsigned nblk = c.nblk;
+  const long c0 = c.c0, c1 = c.c1;
     SoA in = m.view(h, sbuf, abuf, dsbuf, pbuf);
     SoA mid = m.view(h, 1 - sbuf, abuf, 1 - dsbuf, pbuf);
     // single-gas N-S: only the live equations and fields move (SK_SGL/SK_SGT);
@@ -4327,6 +3442,7 @@ void DeviceSolver::step_split(const StepParams& P0, bool want_res, int slot, int
     HIP_CHECK(hipGetLastError());
     dsbuf = 1 - dsbuf;
     pbuf = 1 - pbuf;
+    return {nblk, BLOCK / WAVE, false};
 }
 
 bool DeviceSolver::lns_entry(const StepParams& P0) const {
@@ -4363,9 +3479,31 @@ std::vector<unsigned long long> DeviceSolver::lnm_trace_fetch() {
   return v;
 }
 
-void DeviceSolver::lnm_step(const StepParams& P, bool want_res, int slot, int slot_next, int serial) {
+DeviceSolver::StepDone DeviceSolver::lnm_step(const StepCtx& c) {
   Impl& m = *impl;
   hipStream_t st = m.stream;
+  const StepParams& P = c.P;
+  const bool want_res = c.want_res;
+  const int slot = c.slot, slot_next = c.slot_next, serial = c.serial;
+  if (lean_state) lean_materialize();
+  if (lns_state == 0) {
+    // first lean mechanism step: the split step, then T^{n+1} as the stored state.
+    // Its fill F_{n+1} overwrites the level-n state (Cp, k, p) in place; a
+    // materialise right after this step (a download after a one-step call)
+    // re-runs F_{n+1}, which reads the lagged state from the [cbuf] buffers
+    // as after a lean step: keep level n there (without it the re-fill read
+    // stale buffers: with a download after every step the scramjet's dt
+    // left the CPU stepper's at step 4; test_download_after_every_step_leaves_the_trajectory_unchanged)
+    const size_t SB = (size_t)h.N * sizeof(real);
+    HIP_CHECK(hipMemcpyAsync(m.CP2, m.CP, SB, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.kk2, m.kk, SB, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m.p2, m.p, SB, hipMemcpyDeviceToDevice, st));
+    const StepDone d = step_split(c, true);
+    HIP_CHECK(hipMemcpyAsync(m.Tst[0], m.Tg[pbuf], h.N * sizeof(real), hipMemcpyDeviceToDevice, st));
+    lns_state = 1;
+    cbuf = 1;
+    return d;
+  }
   LnmArrays a = m.lnm_arrays(h, sbuf, pbuf, cbuf, dsbuf, abuf);
   if (std::getenv("HF2D_LNM_TRACE")) {   // phase trace of every step (the last one is kept)
     const long nwg = (long)((P.i1 - P.i0 + lnm_ti - 1) / lnm_ti) * ((P.ny + LNM_TILE - 1) / LNM_TILE);
@@ -4391,50 +3529,26 @@ void DeviceSolver::lnm_step(const StepParams& P, bool want_res, int slot, int sl
   // exchange cost against 17 us for all tiles + push / unpack
   // (tools/exchange_loopback.py, scramjet 8 ranks, profiles/exchange_loopback_r05.md)
   static const bool split_env = std::getenv("HF2D_LNM_SPLIT") && std::string(std::getenv("HF2D_LNM_SPLIT")) == "1";
-  lnm_split = (split_env || lnm_overlap) && comm_overlap && (m.p2p.on ? p2p_fuse : (m.comm || m.local)) && m.nranks > 1 &&
-              !want_res && cs.cfg.isAdiabaticWall;
+  const bool lnm_split = (split_env || lnm_overlap) && comm_overlap &&
+                         (m.p2p.on ? p2p_fuse : (m.comm || m.local)) && m.nranks > 1 && !want_res &&
+                         cs.cfg.isAdiabaticWall;
   const bool parts = T.nbi >= 2 + T.ne;
   // (xGMI mailboxes: the edge halo is pushed before the interior tiles run,
   // and published with the dt once they are done)
-  ColList Lc{};
-  if (lnm_split && m.p2p.on) {
-    sbuf = 1 - sbuf, pbuf = 1 - pbuf, cbuf = 1 - cbuf, dsbuf = 1 - dsbuf;
-    std::vector<real*> fl;
-    std::vector<unsigned char> fo;
-    halo_fields(CpuSolver::HALO_LNS, fl, fo, false);
-    sbuf = 1 - sbuf, pbuf = 1 - pbuf, cbuf = 1 - cbuf, dsbuf = 1 - dsbuf;
-    if (fl.size() > (size_t)MAX_HALO_FIELDS || (long)fl.size() * h.ny > m.halo_cap)
-      throw std::runtime_error("mechanism halo exceeds the mailbox capacity");
-    Lc.nf = (int)fl.size();
-    for (int k = 0; k < Lc.nf; k++) {
-      Lc.f[k] = fl[k];
-      Lc.o[k] = fo[k];
-    }
-  }
+  const ColList Lc = lnm_split && m.p2p.on ? lns_post_list("mechanism") : ColList{};
   if (!lnm_split) {
     a.hot = m.chem_list;
     a.hot_n = &m.sc->hot_cnt[slot];
     a.part = 0;
     // mailboxes: the previous step's halo (pushed after its state kernel,
     // exchange()) is unpacked by this step's edge tiles (fx_ghost_prologue)
-    if (m.p2p.on && p2p_fuse && m.nranks > 1 && lns_prev_valid && lns_ghost_prologue) {
-      a.lg = lc_device(m.lns_pend);
-      if (a.lg) {
-        a.xg = fx_device(fused_args());
-        lns_ghost_pending = false;
-        lns_pro_uses++;
-        lns_prologue_steps++;
-      }
-    }
+    if (m.p2p.on && p2p_fuse && m.nranks > 1) a.lg = claim_ghost_prologue();
+    if (a.lg) a.xg = fx_device(fused_args());
     p2p_complete();
     lnm_launch(P, a, T, want_res, slot, slot_next, serial, (unsigned)(T.nbi * T.nbj));
   } else {
     p2p_complete();
-    if (!m.comm_stream) {
-      HIP_CHECK(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
-      HIP_CHECK(hipEventCreateWithFlags(&m.ev_edge, hipEventDisableTiming));
-      HIP_CHECK(hipEventCreateWithFlags(&m.ev_halo, hipEventDisableTiming));
-    }
+    overlap_streams();
     // edge list first (at most its own cells), the interior list after it:
     // tile column 0 (TI columns), ne - 1 full columns and the last, partial
     // one of w - (nbi - 1) TI columns -- the list holds exactly N entries
@@ -4472,20 +3586,9 @@ void DeviceSolver::lnm_step(const StepParams& P, bool want_res, int slot, int sl
   cbuf = 1 - cbuf;
   dsbuf = 1 - dsbuf;
   lnm_steps++;
-  if (lnm_split && !m.p2p.on) {   // the new state's halo (post-step buffers), overlapped with the interior
-    if (m.local) {   // in-process group: the host orders the streams (see the inviscid path)
-      HIP_CHECK(hipEventSynchronize(m.ev_edge));
-      exchange(CpuSolver::HALO_LNS, -1, (void*)m.comm_stream);
-      HIP_CHECK(hipStreamSynchronize(m.comm_stream));
-    } else {
-      HIP_CHECK(hipStreamWaitEvent(m.comm_stream, m.ev_edge, 0));
-      exchange(CpuSolver::HALO_LNS, -1, (void*)m.comm_stream);
-      HIP_CHECK(hipEventRecord(m.ev_halo, m.comm_stream));
-      HIP_CHECK(hipStreamWaitEvent(st, m.ev_halo, 0));
-    }
-    exchange_dt(slot_next);
-    overlap_steps++;
-  }
+  // the new state's halo (post-step buffers), overlapped with the interior
+  if (lnm_split && !m.p2p.on) overlap_exchange(CpuSolver::HALO_LNS, slot_next);
+  return {(unsigned)(T.nbi * T.nbj), BLOCK / WAVE, lnm_split};
 }
 
 // Tile kernel (the tiles of a.part), kinetics of the cells it listed (a.hot /
@@ -4575,10 +3678,346 @@ bool DeviceSolver::lns_step_ok(const StepParams& P) const {
          P.fpa.is_mu_t == lns_prev_mu_t && P.ny >= LEAN_TILE_MIN_TJ;
 }
 
+// The kernels that run a step with the (completed) parameters P.
+DeviceSolver::StepPath DeviceSolver::step_path(const StepParams& P) const {
+  if (P.sm != SM_NS) {
+    if (lean && lean_ok) return lean_tile && lean_state == 1 && P.ny >= LEAN_TILE_MIN_TJ ? StepPath::Tile : StepPath::LeanFlat;
+    if (fused && !impl->mech) return StepPath::FusedEuler;
+  }
+  return lnm_step_ok(P) ? StepPath::LeanMech : lns_step_ok(P) ? StepPath::LeanNs : StepPath::Split;
+}
+
+// Edge-first steps of the RCCL / in-process transports: the comm stream and
+// the two events that order it against the step's stream.
+void DeviceSolver::overlap_streams() {
+  Impl& m = *impl;
+  if (m.comm_stream) return;
+  HIP_CHECK(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
+  HIP_CHECK(hipEventCreateWithFlags(&m.ev_edge, hipEventDisableTiming));
+  HIP_CHECK(hipEventCreateWithFlags(&m.ev_halo, hipEventDisableTiming));
+}
+
+// The new state's halo of an edge-first step on the comm stream, after the
+// edge part (ev_edge, recorded on the step's stream) and while the interior
+// part runs, then the dt MIN over the ranks into slot_next.
+void DeviceSolver::overlap_exchange(int group, int slot_next) {
+  Impl& m = *impl;
+  if (m.local) {
+    // in-process group: the host orders the two streams (waits on it).
+    // Device-side cross-stream waits would put barrier packets in hardware
+    // queues that several virtual ranks' streams share, and a wait cycle
+    // across those queues can deadlock.
+    HIP_CHECK(hipEventSynchronize(m.ev_edge));
+    exchange(group, -1, (void*)m.comm_stream);
+    HIP_CHECK(hipStreamSynchronize(m.comm_stream));
+  } else {
+    HIP_CHECK(hipStreamWaitEvent(m.comm_stream, m.ev_edge, 0));
+    exchange(group, -1, (void*)m.comm_stream);
+    HIP_CHECK(hipEventRecord(m.ev_halo, m.comm_stream));
+    HIP_CHECK(hipStreamWaitEvent(m.stream, m.ev_halo, 0));
+  }
+  exchange_dt(slot_next);
+  overlap_steps++;
+}
+
+// The HALO_LNS pointers of the post-step buffers (a fused step pushes the
+// state it is about to write).
+ColList DeviceSolver::lns_post_list(const char* what) const {
+  std::vector<real*> fl;
+  std::vector<unsigned char> fo;
+  halo_fields_lns(fl, fo, 1 - sbuf, 1 - pbuf, 1 - cbuf, 1 - dsbuf);
+  if (fl.size() > (size_t)MAX_HALO_FIELDS || (long)fl.size() * h.ny > impl->halo_cap)
+    throw std::runtime_error(std::string(what) + " halo exceeds the mailbox capacity");
+  ColList Lc{};
+  Lc.nf = (int)fl.size();
+  for (int k = 0; k < Lc.nf; k++) {
+    Lc.f[k] = fl[k];
+    Lc.o[k] = fo[k];
+  }
+  return Lc;
+}
+
+// The previous fused step's halo is still in the mailbox: this step's edge
+// tiles copy it into the ghost columns they read (fx_ghost_prologue) instead
+// of a separate unpack launch.  Valid whenever the mailbox's last
+// publication was a fused lean N-S / mechanism step: its parity stays
+// untouched until this step publishes, so the copy is exact even if
+// p2p_complete already unpacked it.  nullptr (a list new inside a capture,
+// or no such publication): the separate unpack of p2p_complete.
+const ColList* DeviceSolver::claim_ghost_prologue() {
+  if (!lns_prev_valid || !lns_ghost_prologue) return nullptr;
+  const ColList* Lg = lc_device(impl->lns_pend);
+  if (Lg) {
+    lns_ghost_pending = false;
+    lns_pro_uses++;
+    lns_prologue_steps++;
+  }
+  return Lg;
+}
+
+// Inviscid lean tile step (lean_tile.hpp).
+DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
+  Impl& m = *impl;
+  hipStream_t st = m.stream;
+  StepParams& P = c.P;   // (the tile kernel's own flags are set below)
+  const bool want_res = c.want_res;
+  const int slot = c.slot, slot_next = c.slot_next, serial = c.serial;
+  LeanSoA L = m.lean_view(h, sbuf, abuf, dsbuf, pbuf, false);
+  P.skip_same = tile_skip_same ? 1 : 0;
+  P.dt_read = dt_read_mode == 1 ? 1 : 0;
+  // two cells per thread unless that leaves fewer than ~2 workgroups per CU
+  // (small strips of a multi-GPU run)
+  // (256-thread tiles only: the small-workgroup geometries are explicit
+  // choices of the autotune)
+  const bool sg = lean_sg && lean_sg_ok;
+  const int nt = tile_nt(lean_nt, sg);
+  int cpt = lean_cpt == 2 ? 2 : 1;
+  if (cpt == 2 && nt == BLOCK) {
+    const LeanTile T2 = lean_tile_geom(P.i1 - P.i0, P.ny, BLOCK, lean_tj, 2);
+    if ((long)T2.nbi * T2.nbj < 2L * cu_count) cpt = 1;
+  }
+  const LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, nt, lean_tj, cpt);
+  const unsigned ntile = (unsigned)(T.nbi * T.nbj);
+  size_t shmem = (size_t)lean_tile_fields(sg) * T.NC * sizeof(real);
+  if (lean_wgcu > 0)   // cap the resident workgroups per CU through the LDS request (160 KB per CU)
+    shmem = std::max(shmem, (size_t)((LDS_PER_CU / lean_wgcu - 1024) & ~255));
+  // an armed recorder needs T of every step, which the plain variant does
+  // not store: where R is constant over a tile step (single gas, or no
+  // reactions) the recorder forms it from p, R, rho; a reacting mixture
+  // runs the output variant instead
+  const bool rec_out = (probe_cap > 0 || stats_on) && !sg && P.chem_model != NO_REACTIONS;
+  const bool out = step_outputs || want_res || rec_out;
+  // staggered start only for a grid that is resident at once (<= 4 dispatch
+  // rounds: measured 1.5 us faster on the headline grid; the 4000x1000 triple
+  // point, dispatched in ~15 waves, ran 350 -> 550 us with it)
+  P.stagger_wgs = cu_count > 0 ? cu_count : 256;
+  P.stagger = ntile <= 4u * (unsigned)P.stagger_wgs && nt == BLOCK ? tile_stagger : 0;
+  // (64-thread tiles, the whole grid resident at once: a linear start ramp
+  // over the grid of 2 / 4 / 7 / 10 us measured 4.7 / 6.4 / 15 / 27 %
+  // slower than none, profiles/r04_start.md)
+  // multi-GPU: exchange fused into the tile kernel (no separate exchange launch)
+  const bool fx_step = m.p2p.on && p2p_fuse && !lean_has_cauchy_x;
+  FusedX X = fx_step ? fused_args() : FusedX{};
+  // lagged dt: the fused tail waits for the two neighbours only; the dt
+  // MIN follows in the next fused step's first workgroup or in
+  // hf2d_p2p_complete before any other consumer (fx_pending)
+  X.defer = fx_step && P.lag_dt ? 1 : 0;
+  lean_tile_last.nt = nt;
+  lean_tile_last.cpt = cpt;
+  lean_tile_last.TI = T.TI;
+  lean_tile_last.TJ = T.TJ;
+  lean_tile_last.nbi = T.nbi;
+  lean_tile_last.nbj = T.nbj;
+  // (the stagger block is compiled into the single-gas two-cell 256-thread plain kernel only)
+  lean_tile_last.stagger = HF2D_TILE_STAGGER && sg && cpt == 2 && !fx_step && nt == BLOCK ? P.stagger : 0;
+  lean_tile_last.fx = fx_step ? 1 : 0;
+  lean_tile_last.seen = c.tile_prev.nt == nt && c.tile_prev.cpt == cpt ? c.tile_prev.seen : 0;
+  // RCCL / in-process transports: edge tiles first, their halo on the comm
+  // stream while the interior tiles compute, then the dt MIN
+  // (the decision must be the same on every rank -- the exchange sequence
+  // differs -- so a strip too narrow to split runs all its tiles at once)
+  const bool split = comm_overlap && !fx_step && !m.p2p.on && (m.comm || m.local) && m.nranks > 1 &&
+                     !want_res && !out && !tile_trace && lean_occ == 0;
+  if (split) {
+    lean_tile_last.seen |= 1;   // (the part launches are plain steps)
+    lean_T_stored = false;
+    overlap_streams();
+    const bool parts = T.nbi >= 3;
+    const unsigned ne = parts ? (unsigned)(2 * T.nbj) : ntile, ni = parts ? (unsigned)((T.nbi - 2) * T.nbj) : 0u;
+    const TileK pk = tile_kernel(nt, sg, cpt, 0);
+    hipLaunchKernelGGL(pk, dim3(ne), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials,
+                       parts ? 1 : 0);
+    HIP_CHECK(hipGetLastError());
+    sbuf = 1 - sbuf;   // the new state is this step's output arrays
+    dsbuf = 1 - dsbuf;
+    pbuf = 1 - pbuf;
+    HIP_CHECK(hipEventRecord(m.ev_edge, st));
+    // interior tiles in flight before the (possibly host-blocking) exchange
+    // is issued; they write neither the edge columns nor the ghost columns
+    if (ni > 0)
+      hipLaunchKernelGGL(pk, dim3(ni), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials,
+                         2);
+    HIP_CHECK(hipGetLastError());
+    overlap_exchange(CpuSolver::HALO_LEAN, slot_next);
+    return {ntile, nt / WAVE, true};
+  }
+  // variant: 0 plain, 1 outputs, 2 residual (all variants of one step use
+  // the cpt the tile geometry was built for)
+  const int var = want_res ? 2 : out ? 1 : 0;
+  lean_tile_last.var = var;
+  lean_tile_last.seen |= 1 << var;
+  lean_T_stored = var != 0;
+  if (tile_trace && var == 0 && !fx_step)
+    hipLaunchKernelGGL(tile_tr_kernel(nt, sg, cpt), dim3(ntile), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next,
+                       serial, m.partials, tile_trace);
+  else if (fx_step) {
+    // the fused tail folds every rank's dt into the next slot's word
+    // (fx_tail): the next fused step reads that one word (not when the
+    // fold is deferred, lagged dt)
+    const bool word = dt_read_mode >= 1 && !X.defer;
+    if (word && c.dt_word_ok) P.dt_read = 2;
+    lean_tile_last.dt_read = P.dt_read;
+    hipLaunchKernelGGL(tile_fx_kernel(nt, sg, cpt, var), dim3(ntile), dim3(nt), shmem, st, P, L, T, m.sc, slot,
+                       slot_next, serial, m.partials, fx_device(X));
+    dt_word_valid = word;
+    fx_pending = true;   // exchanged inside the tile kernel
+  } else if (sg && cpt == 1 && var == 0 && lean_occ == 6 && !tile_trace && nt == BLOCK)
+    hipLaunchKernelGGL((hf2d_lean_tile_occ<false, false, true, 6>), dim3(ntile), dim3(BLOCK), shmem, st, P, L, T,
+                       m.sc, slot, slot_next, serial, m.partials);
+  // (multi-gas, one cell per thread, at a 5-wave register budget -- 96
+  // VGPRs + 10 spilled instead of 103: the triple point ran 351 -> 365 us)
+  else {
+    // single GPU, last step of the host call: the scalars go to the host
+    // mirror from the kernel's own tail (host_tail)
+    const bool mirror = var == 1 && step_outputs && !tile_trace && host_tail && m.nranks == 1 && !m.local && !m.p2p.on;
+    if (mirror) {
+      P.host_sc = m.sc_host;
+      P.host_done = m.host_done;
+    }
+    // dt read of the tile kernel (StepParams::dt_read): with dt_read_mode
+    // 2 every step's last workgroup folds the shards into the word and the
+    // next step's workgroups read that one word
+    const bool fold = dt_read_mode == 2 && !tile_trace && m.nranks == 1 && !m.local && !m.p2p.on;
+    P.dt_read = (fold && c.dt_word_ok) ? 2 : dt_read_mode == 1 ? 1 : 0;
+    if (fold) {
+      P.dt_fold = 1;
+      P.host_done = m.host_done;
+    }
+    lean_tile_last.dt_read = P.dt_read;
+    hipLaunchKernelGGL(tile_kernel(nt, sg, cpt, var), dim3(ntile), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next,
+                       serial, m.partials, 0);
+    m.sc_mirrored = mirror;
+    dt_word_valid = fold;
+  }
+  HIP_CHECK(hipGetLastError());
+  sbuf = 1 - sbuf;
+  dsbuf = 1 - dsbuf;
+  pbuf = 1 - pbuf;
+  return {ntile, nt / WAVE, fx_step};
+}
+
+// Flat lean Euler step (the first lean step, or every one without lean_tile).
+DeviceSolver::StepDone DeviceSolver::step_lean_flat(const StepCtx& c) {
+  Impl& m = *impl;
+  const bool fromg = lean_state == 0;
+  LeanSoA L = m.lean_view(h, sbuf, abuf, dsbuf, pbuf, fromg);
+  hipLaunchKernelGGL(kLeanEuler[c.want_res][fromg], dim3(c.nblk), dim3(BLOCK), 0, m.stream, c.P, L, c.c0, c.c1, m.sc,
+                     c.slot, c.slot_next, c.serial, m.partials);
+  HIP_CHECK(hipGetLastError());
+  sbuf = 1 - sbuf;
+  dsbuf = 1 - dsbuf;
+  pbuf = 1 - pbuf;
+  lean_state = 1;
+  lean_T_stored = true;   // (the flat kernel always writes the output-only fields)
+  return {c.nblk, BLOCK / WAVE, false};
+}
+
+DeviceSolver::StepDone DeviceSolver::step_fused_euler(const StepCtx& c) {
+  Impl& m = *impl;
+  if (lean_state) lean_materialize();
+  // Predictor and fill of a cell run back to back in one thread, so the
+  // new state goes to the other S buffer (neighbours still read the old
+  // one) and the current-state index flips.
+  SoA in = m.view(h, sbuf, abuf, dsbuf, pbuf);
+  SoA mid = m.view(h, 1 - sbuf, abuf, 1 - dsbuf, pbuf);
+  SoA out = m.view(h, 1 - sbuf, 1 - abuf, 1 - dsbuf, pbuf);
+  hipLaunchKernelGGL(c.want_res ? hf2d_fused_euler<true> : hf2d_fused_euler<false>, dim3(c.nblk), dim3(BLOCK), 0,
+                     m.stream, c.P, in, mid, out, c.c0, c.c1, m.sc, c.slot, c.slot_next, c.serial, m.partials);
+  HIP_CHECK(hipGetLastError());
+  abuf = 1 - abuf;
+  dsbuf = 1 - dsbuf;
+  sbuf = 1 - sbuf;
+  return {c.nblk, BLOCK / WAVE, false};
+}
+
+// Lean N-S step (lean_ns.hpp), with its entry step.
+DeviceSolver::StepDone DeviceSolver::step_lean_ns(const StepCtx& c) {
+  Impl& m = *impl;
+  hipStream_t st = m.stream;
+  const StepParams& P = c.P;
+  const bool want_res = c.want_res;
+  const int slot = c.slot, slot_next = c.slot_next, serial = c.serial;
+  if (lean_state) lean_materialize();
+  if (lns_state == 0) {
+    // first lean N-S step: the split step with the fill's CP/mu/lam/k going
+    // to the second level buffers (the level it read stays for K_{n+1})
+    const StepDone d = step_split(c, true);
+    lns_state = 1;
+    cbuf = 1;
+    return d;
+  }
+  const LnsArrays a = m.lns_arrays(h, sbuf, pbuf, cbuf, dsbuf, abuf);
+  LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, BLOCK, lean_tj > 0 ? lean_tj : lns_tile_height(P.ny, BLOCK), 1);
+  // (the halo's second column must come from the edge part)
+  T.ne = (P.i1 - P.i0) % T.TI == 1 ? 2 : 1;
+  const int ntile = T.nbi * T.nbj;
+  const bool t2 = sk_mode == SK_SGT;
+  const size_t shmem = (size_t)(t2 ? Lns<SK_SGT>::PLANES : Lns<SK_SGL>::PLANES) * T.NC * sizeof(real);
+  // register budget (measured, 1x MI355X): the k-eps kernel compiles to
+  // ~173 VGPRs (2 waves/SIMD); a 3-wave budget is 11 % faster (resonator
+  // 2000x200: 110.7 -> 98.8 us/step); the laminar one is best unbounded
+  const int occ = lns_occ > 0 ? lns_occ : (t2 ? 3 : 0);
+  // (a residual step runs the compiler's register budget)
+  const int tv = !t2 ? 0 : lns_turb == 3 ? 2 : lns_turb == 4 ? 3 : 1;
+  const LnsK lk = kLns[tv][want_res][want_res ? 0 : (occ == 5 ? 2 : occ == 3 ? 1 : 0)];
+  // xGMI mailboxes: the exchange fused into the tile kernel (edge cells
+  // push their HALO_LNS values to the neighbour, the last workgroup
+  // publishes the step and folds the peers' dt), then one unpack kernel;
+  // RCCL / in-process transports: edge tiles first, their halo on the comm
+  // stream while the interior tiles compute, then the dt MIN (as the
+  // inviscid tile kernel)
+  const bool lns_fx = m.p2p.on && p2p_fuse && m.nranks > 1;
+  const ColList Lc = lns_fx ? lns_post_list("lean N-S") : ColList{};
+  // (the decision must be the same on every rank -- the exchange sequence
+  // differs -- so a strip too narrow to split runs all its tiles at once)
+  const bool lns_split = !lns_fx && comm_overlap && !m.p2p.on && (m.comm || m.local) && m.nranks > 1 && !want_res &&
+                         cs.cfg.isAdiabaticWall;
+  const bool lparts = T.nbi >= 2 + T.ne;
+  if (lns_fx) {
+    const ColList* Lg = claim_ghost_prologue();
+    p2p_complete();   // (a list new inside a capture: the separate unpack)
+    hipLaunchKernelGGL(kLnsFx[tv][want_res ? 1 : 0], dim3(ntile), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot,
+                       slot_next, serial, m.partials, fused_args(), Lc, Lg);
+    HIP_CHECK(hipGetLastError());
+    m.lns_pend = Lc;
+    lns_ghost_pending = lns_last_valid = true;   // unpacked by the next fused step or p2p_complete
+    if (lns_ghost_prologue) (void)lc_device(Lc);   // (uploaded now, outside any capture, when eager)
+    ghost_stale = true;   // lean representation in the ghosts
+    lns_fx_steps++;
+  } else if (lns_split) {
+    overlap_streams();
+    hipLaunchKernelGGL(lk, dim3(lparts ? (1 + T.ne) * T.nbj : ntile), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot,
+                       slot_next, serial, m.partials, lparts ? 1 : 0);
+  } else {
+    hipLaunchKernelGGL(lk, dim3(ntile), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot, slot_next, serial,
+                       m.partials, 0);
+  }
+  HIP_CHECK(hipGetLastError());
+  sbuf = 1 - sbuf;
+  pbuf = 1 - pbuf;
+  cbuf = 1 - cbuf;
+  dsbuf = 1 - dsbuf;
+  lns_steps++;
+  if (lns_split) {
+    HIP_CHECK(hipEventRecord(m.ev_edge, st));
+    // interior tiles in flight before the exchange is issued; they write
+    // neither the edge columns nor the ghost columns
+    if (lparts)
+      hipLaunchKernelGGL(lk, dim3((T.nbi - 1 - T.ne) * T.nbj), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot,
+                         slot_next, serial, m.partials, 2);
+    HIP_CHECK(hipGetLastError());
+    overlap_exchange(CpuSolver::HALO_LNS, slot_next);
+  }
+  // (fused: exchanged inside the kernel, unpacked by the next step or p2p_complete)
+  return {(unsigned)ntile, BLOCK / WAVE, lns_fx || lns_split};
+}
+
 StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   Impl& m = *impl;
+  hipStream_t st = m.stream;
   m.sc_mirrored = false;
-  StepParams P = P0;
+  StepCtx c{P0, want_res};
+  StepParams& P = c.P;
   P.nx = h.nx;
   P.ny = h.ny;
   P.i0 = l_off;
@@ -4587,379 +4026,52 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   P.do_residual = want_res ? 1 : 0;
   P.species = m.species;
   P.scen = m.scen;
-  const long c0 = (long)P.i0 * P.ny, c1 = (long)P.i1 * P.ny;
-  const unsigned nblk = (unsigned)((c1 - c0 + BLOCK - 1) / BLOCK);
-  const int slot = nstep % 3, slot_next = (nstep + 1) % 3;
-  const int serial = cs.cfg.semantics == Semantics::SERIAL ? 1 : 0;
-  const bool euler = P.sm != SM_NS;
-  hipStream_t st = m.stream;
-  unsigned nres = nblk;   // workgroups that wrote residual partials
-  int nres_waves = BLOCK / WAVE;   // ... and partials per workgroup
-  const bool sg_now = lean_sg && lean_sg_ok;
-  fx_step = false;
+  c.c0 = (long)P.i0 * P.ny;
+  c.c1 = (long)P.i1 * P.ny;
+  c.nblk = (unsigned)((c.c1 - c.c0 + BLOCK - 1) / BLOCK);
+  c.slot = nstep % 3;
+  c.slot_next = (nstep + 1) % 3;
+  c.serial = cs.cfg.semantics == Semantics::SERIAL ? 1 : 0;
   // the slot's word holds the MIN only right after a folding tile launch
-  const bool dt_word_ok = dt_word_valid;
+  c.dt_word_ok = dt_word_valid;
   dt_word_valid = false;
   // the mailbox holds a fused lean N-S step's halo (list m.lns_pend) only
   // right after such a step (every other step or exchange publishes another
   // layout or nothing)
   lns_prev_valid = lns_last_valid;
   lns_last_valid = false;
-  const TileLast tile_prev = lean_tile_last;
+  c.tile_prev = lean_tile_last;
   lean_tile_last = TileLast{};
-  const bool tile_path = euler && lean && lean_ok && lean_tile &&
-                         lean_state == 1 && P.ny >= LEAN_TILE_MIN_TJ;
-  // (a fused lean N-S step unpacks the previous fused step's halo itself)
-  const bool lns_fx_next = !euler && (lnm_step_ok(P) || lns_step_ok(P)) && lns_state == 1 && lean_state == 0 &&
-                           m.p2p.on && p2p_fuse && m.nranks > 1;
-  if (!tile_path) p2p_complete(lns_fx_next);
-  if (euler && lean && lean_ok && lean_tile && lean_state == 1 && P.ny >= LEAN_TILE_MIN_TJ) {
-    LeanSoA L = m.lean_view(h, sbuf, abuf, dsbuf, pbuf, false);
-    P.skip_same = tile_skip_same ? 1 : 0;
-    P.dt_read = dt_read_mode == 1 ? 1 : 0;
-    // two cells per thread unless that leaves fewer than ~2 workgroups per CU
-    // (small strips of a multi-GPU run)
-    // (256-thread tiles only: the small-workgroup geometries are explicit
-    // choices of the autotune)
-    const bool sg = lean_sg && lean_sg_ok;
-    const int nt = tile_nt(lean_nt, sg), nts = nt == 128 ? 0 : 1;
-    int cpt = lean_cpt == 2 ? 2 : 1;
-    if (cpt == 2 && nt == BLOCK) {
-      const LeanTile T2 = lean_tile_geom(P.i1 - P.i0, P.ny, BLOCK, lean_tj, 2);
-      if ((long)T2.nbi * T2.nbj < 2L * cu_count) cpt = 1;
-    }
-    const LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, nt, lean_tj, cpt);
-    const unsigned ntile = (unsigned)(T.nbi * T.nbj);
-    size_t shmem = (size_t)lean_tile_fields(sg) * T.NC * sizeof(real);
-    if (lean_wgcu > 0)   // cap the resident workgroups per CU through the LDS request (160 KB per CU)
-      shmem = std::max(shmem, (size_t)((LDS_PER_CU / lean_wgcu - 1024) & ~255));
-    // an armed recorder needs T of every step, which the plain variant does
-    // not store: where R is constant over a tile step (single gas, or no
-    // reactions) the recorder forms it from p, R, rho; a reacting mixture
-    // runs the output variant instead
-    const bool rec_out = (probe_cap > 0 || stats_on) && !sg && P.chem_model != NO_REACTIONS;
-    const bool out = step_outputs || want_res || rec_out;
-    // staggered start only for a grid that is resident at once (<= 4 dispatch
-    // rounds: measured 1.5 us faster on the headline grid; the 4000x1000 triple
-    // point, dispatched in ~15 waves, ran 350 -> 550 us with it)
-    P.stagger_wgs = cu_count > 0 ? cu_count : 256;
-    P.stagger = ntile <= 4u * (unsigned)P.stagger_wgs && nt == BLOCK ? tile_stagger : 0;
-    // (64-thread tiles, the whole grid resident at once: a linear start ramp
-    // over the grid of 2 / 4 / 7 / 10 us measured 4.7 / 6.4 / 15 / 27 %
-    // slower than none, profiles/r04_start.md)
-    // multi-GPU: exchange fused into the tile kernel (no separate exchange launch)
-    fx_step = m.p2p.on && p2p_fuse && !lean_has_cauchy_x;
-    FusedX X = fx_step ? fused_args() : FusedX{};
-    // lagged dt: the fused tail waits for the two neighbours only; the dt
-    // MIN follows in the next fused step's first workgroup or in
-    // hf2d_p2p_complete before any other consumer (fx_pending)
-    X.defer = fx_step && P.lag_dt ? 1 : 0;
-    lean_tile_last.nt = nt;
-    lean_tile_last.cpt = cpt;
-    lean_tile_last.TI = T.TI;
-    lean_tile_last.TJ = T.TJ;
-    lean_tile_last.nbi = T.nbi;
-    lean_tile_last.nbj = T.nbj;
-    // (the stagger block is compiled into the single-gas two-cell 256-thread plain kernel only)
-    lean_tile_last.stagger = HF2D_TILE_STAGGER && sg && cpt == 2 && !fx_step && nt == BLOCK ? P.stagger : 0;
-    lean_tile_last.fx = fx_step ? 1 : 0;
-    lean_tile_last.seen = tile_prev.nt == nt && tile_prev.cpt == cpt ? tile_prev.seen : 0;
-    // RCCL / in-process transports: edge tiles first, their halo on the comm
-    // stream while the interior tiles compute, then the dt MIN
-    // (the decision must be the same on every rank -- the exchange sequence
-    // differs -- so a strip too narrow to split runs all its tiles at once)
-    const bool split = comm_overlap && !fx_step && !m.p2p.on && (m.comm || m.local) && m.nranks > 1 &&
-                       !want_res && !out && !tile_trace && lean_occ == 0;
-    if (split) {
-      lean_tile_last.seen |= 1;   // (the part launches are plain steps)
-      lean_T_stored = false;
-      if (!m.comm_stream) {
-        HIP_CHECK(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
-        HIP_CHECK(hipEventCreateWithFlags(&m.ev_edge, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&m.ev_halo, hipEventDisableTiming));
-      }
-      const bool parts = T.nbi >= 3;
-      const unsigned ne = parts ? (unsigned)(2 * T.nbj) : ntile, ni = parts ? (unsigned)((T.nbi - 2) * T.nbj) : 0u;
-      const TileK pk = nt == BLOCK ? kTile[sg][cpt - 1][0] : kTileNt[nts][cpt - 1][0];
-      hipLaunchKernelGGL(pk, dim3(ne), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials,
-                         parts ? 1 : 0);
-      HIP_CHECK(hipGetLastError());
-      sbuf = 1 - sbuf;   // the new state is this step's output arrays
-      dsbuf = 1 - dsbuf;
-      pbuf = 1 - pbuf;
-      HIP_CHECK(hipEventRecord(m.ev_edge, st));
-      // interior tiles in flight before the (possibly host-blocking) exchange
-      // is issued; they write neither the edge columns nor the ghost columns
-      if (ni > 0)
-        hipLaunchKernelGGL(pk, dim3(ni), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials,
-                           2);
-      HIP_CHECK(hipGetLastError());
-      if (m.local) {
-        // in-process group: the host orders the two streams (waits on it).
-        // Device-side cross-stream waits would put barrier packets in hardware
-        // queues that several virtual ranks' streams share, and a wait cycle
-        // across those queues can deadlock.
-        HIP_CHECK(hipEventSynchronize(m.ev_edge));
-        exchange(CpuSolver::HALO_LEAN, -1, (void*)m.comm_stream);
-        HIP_CHECK(hipStreamSynchronize(m.comm_stream));
-      } else {
-        HIP_CHECK(hipStreamWaitEvent(m.comm_stream, m.ev_edge, 0));
-        exchange(CpuSolver::HALO_LEAN, -1, (void*)m.comm_stream);
-        HIP_CHECK(hipEventRecord(m.ev_halo, m.comm_stream));
-        HIP_CHECK(hipStreamWaitEvent(st, m.ev_halo, 0));
-      }
-      exchange_dt(slot_next);
-      overlap_steps++;
-      if (probe_cap) launch_probe_record(P);
-      if (stats_on) launch_stats(P);
-      nstep++;
-      StepResult r;
-      r.async = true;
-      return r;
-    }
-    // variant: 0 plain, 1 outputs, 2 residual (all variants of one step use
-    // the cpt the tile geometry was built for)
-    const int var = want_res ? 2 : out ? 1 : 0;
-    lean_tile_last.var = var;
-    lean_tile_last.seen |= 1 << var;
-    lean_T_stored = var != 0;
-    if (tile_trace && var == 0 && !fx_step)
-      hipLaunchKernelGGL(nt == BLOCK ? kTileTr[sg][cpt - 1] : kTileTrNt[nts][cpt - 1], dim3(ntile), dim3(nt), shmem,
-                         st, P, L, T, m.sc, slot, slot_next, serial, m.partials, tile_trace);
-    else if (fx_step) {
-      // the fused tail folds every rank's dt into the next slot's word
-      // (fx_tail): the next fused step reads that one word (not when the
-      // fold is deferred, lagged dt)
-      const bool word = dt_read_mode >= 1 && !X.defer;
-      if (word && dt_word_ok) P.dt_read = 2;
-      lean_tile_last.dt_read = P.dt_read;
-      hipLaunchKernelGGL(nt == BLOCK ? kTileFx[sg][cpt - 1][var] : kTileFxNt[nts][cpt - 1][var], dim3(ntile),
-                         dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials, fx_device(X));
-      dt_word_valid = word;
-    } else if (sg && cpt == 1 && var == 0 && lean_occ == 6 && !tile_trace && nt == BLOCK)
-      hipLaunchKernelGGL((hf2d_lean_tile_occ<false, false, true, 6>), dim3(ntile), dim3(BLOCK), shmem, st, P, L, T,
-                         m.sc, slot, slot_next, serial, m.partials);
-    // (multi-gas, one cell per thread, at a 5-wave register budget -- 96
-    // VGPRs + 10 spilled instead of 103: the triple point ran 351 -> 365 us)
-    else {
-      // single GPU, last step of the host call: the scalars go to the host
-      // mirror from the kernel's own tail (host_tail)
-      const bool mirror = var == 1 && step_outputs && !tile_trace && host_tail && m.nranks == 1 && !m.local && !m.p2p.on;
-      if (mirror) {
-        P.host_sc = m.sc_host;
-        P.host_done = m.host_done;
-      }
-      // dt read of the tile kernel (StepParams::dt_read): with dt_read_mode
-      // 2 every step's last workgroup folds the shards into the word and the
-      // next step's workgroups read that one word
-      const bool fold = dt_read_mode == 2 && !tile_trace && m.nranks == 1 && !m.local && !m.p2p.on;
-      P.dt_read = (fold && dt_word_ok) ? 2 : dt_read_mode == 1 ? 1 : 0;
-      if (fold) {
-        P.dt_fold = 1;
-        P.host_done = m.host_done;
-      }
-      lean_tile_last.dt_read = P.dt_read;
-      if (nt != BLOCK)
-        hipLaunchKernelGGL(kTileNt[nts][cpt - 1][var], dim3(ntile), dim3(nt), shmem, st, P, L, T, m.sc, slot,
-                           slot_next, serial, m.partials, 0);
-      else
-        hipLaunchKernelGGL(kTile[sg][cpt - 1][var], dim3(ntile), dim3(BLOCK), shmem, st, P, L, T, m.sc, slot,
-                           slot_next, serial, m.partials, 0);
-      m.sc_mirrored = mirror;
-      dt_word_valid = fold;
-    }
-    HIP_CHECK(hipGetLastError());
-    nres = ntile;
-    nres_waves = nt / WAVE;
-    sbuf = 1 - sbuf;
-    dsbuf = 1 - dsbuf;
-    pbuf = 1 - pbuf;
-  } else if (euler && lean && lean_ok) {
-    const bool fromg = lean_state == 0;
-    LeanSoA L = m.lean_view(h, sbuf, abuf, dsbuf, pbuf, fromg);
-    hipLaunchKernelGGL(kLeanEuler[want_res][fromg], dim3(nblk), dim3(BLOCK), 0, st, P, L, c0, c1, m.sc, slot,
-                       slot_next, serial, m.partials);
-    HIP_CHECK(hipGetLastError());
-    sbuf = 1 - sbuf;
-    dsbuf = 1 - dsbuf;
-    pbuf = 1 - pbuf;
-    lean_state = 1;
-    lean_T_stored = true;   // (the flat kernel always writes the output-only fields)
-  } else if (euler && fused && !m.mech) {
-    if (lean_state) lean_materialize();
-    // Predictor and fill of a cell run back to back in one thread, so the
-    // new state goes to the other S buffer (neighbours still read the old
-    // one) and the current-state index flips.
-    SoA in = m.view(h, sbuf, abuf, dsbuf, pbuf);
-    SoA mid = m.view(h, 1 - sbuf, abuf, 1 - dsbuf, pbuf);
-    SoA out = m.view(h, 1 - sbuf, 1 - abuf, 1 - dsbuf, pbuf);
-    hipLaunchKernelGGL(want_res ? hf2d_fused_euler<true> : hf2d_fused_euler<false>, dim3(nblk), dim3(BLOCK), 0, st,
-                       P, in, mid, out, c0, c1, m.sc, slot, slot_next, serial, m.partials);
-    HIP_CHECK(hipGetLastError());
-    abuf = 1 - abuf;
-    dsbuf = 1 - dsbuf;
-    sbuf = 1 - sbuf;
-  } else if (lnm_step_ok(P)) {
-    if (lean_state) lean_materialize();
-    if (lns_state == 0) {
-      // first lean mechanism step: the split step, then T^{n+1} as the stored state.
-      // Its fill F_{n+1} overwrites the level-n state (Cp, k, p) in place; a
-      // materialise right after this step (a download after a one-step call)
-      // re-runs F_{n+1}, which reads the lagged state from the [cbuf] buffers
-      // as after a lean step: keep level n there (without it the re-fill read
-      // stale buffers: with a download after every step the scramjet's dt
-      // left the CPU stepper's at step 4; test_download_after_every_step_leaves_the_trajectory_unchanged)
-      const size_t SB = (size_t)h.N * sizeof(real);
-      HIP_CHECK(hipMemcpyAsync(m.CP2, m.CP, SB, hipMemcpyDeviceToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(m.kk2, m.kk, SB, hipMemcpyDeviceToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(m.p2, m.p, SB, hipMemcpyDeviceToDevice, st));
-      step_split(P, want_res, slot, slot_next, serial, nblk, true);
-      HIP_CHECK(hipMemcpyAsync(m.Tst[0], m.Tg[pbuf], h.N * sizeof(real), hipMemcpyDeviceToDevice, st));
-      lns_state = 1;
-      cbuf = 1;
-    } else {
-      lnm_step(P, want_res, slot, slot_next, serial);
-      const LeanTile T = lnm_tile(P.i1 - P.i0, P.ny, lnm_ti);
-      nres = (unsigned)(T.nbi * T.nbj);
-    }
-  } else if (lns_step_ok(P)) {
-    if (lean_state) lean_materialize();
-    if (lns_state == 0) {
-      // first lean N-S step: the split step with the fill's CP/mu/lam/k going
-      // to the second level buffers (the level it read stays for K_{n+1})
-      step_split(P, want_res, slot, slot_next, serial, nblk, true);
-      lns_state = 1;
-      cbuf = 1;
-    } else {
-      const LnsArrays a = m.lns_arrays(h, sbuf, pbuf, cbuf, dsbuf, abuf);
-      LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, BLOCK, lean_tj > 0 ? lean_tj : lns_tile_height(P.ny, BLOCK), 1);
-      // (the halo's second column must come from the edge part)
-      T.ne = (P.i1 - P.i0) % T.TI == 1 ? 2 : 1;
-      const int ntile = T.nbi * T.nbj;
-      const bool t2 = sk_mode == SK_SGT;
-      const size_t shmem = (size_t)(t2 ? Lns<SK_SGT>::PLANES : Lns<SK_SGL>::PLANES) * T.NC * sizeof(real);
-      // register budget (measured, 1x MI355X): the k-eps kernel compiles to
-      // ~173 VGPRs (2 waves/SIMD); a 3-wave budget is 11 % faster (resonator
-      // 2000x200: 110.7 -> 98.8 us/step); the laminar one is best unbounded
-      const int occ = lns_occ > 0 ? lns_occ : (t2 ? 3 : 0);
-      // (a residual step runs the compiler's register budget)
-      const int tv = !t2 ? 0 : lns_turb == 3 ? 2 : lns_turb == 4 ? 3 : 1;
-      const LnsK lk = kLns[tv][want_res][want_res ? 0 : (occ == 5 ? 2 : occ == 3 ? 1 : 0)];
-      // xGMI mailboxes: the exchange fused into the tile kernel (edge cells
-      // push their HALO_LNS values to the neighbour, the last workgroup
-      // publishes the step and folds the peers' dt), then one unpack kernel;
-      // RCCL / in-process transports: edge tiles first, their halo on the comm
-      // stream while the interior tiles compute, then the dt MIN (as the
-      // inviscid tile kernel)
-      ColList Lc{};
-      lns_fx = m.p2p.on && p2p_fuse && m.nranks > 1;
-      if (lns_fx) {   // the HALO_LNS pointers of the post-step buffers
-        sbuf = 1 - sbuf, pbuf = 1 - pbuf, cbuf = 1 - cbuf, dsbuf = 1 - dsbuf;
-        std::vector<real*> fl;
-        std::vector<unsigned char> fo;
-        halo_fields(CpuSolver::HALO_LNS, fl, fo, false);
-        sbuf = 1 - sbuf, pbuf = 1 - pbuf, cbuf = 1 - cbuf, dsbuf = 1 - dsbuf;
-        if (fl.size() > (size_t)MAX_HALO_FIELDS || (long)fl.size() * h.ny > m.halo_cap)
-          throw std::runtime_error("lean N-S halo exceeds the mailbox capacity");
-        Lc.nf = (int)fl.size();
-        for (int k = 0; k < Lc.nf; k++) {
-          Lc.f[k] = fl[k];
-          Lc.o[k] = fo[k];
-        }
-      }
-      // (the decision must be the same on every rank -- the exchange sequence
-      // differs -- so a strip too narrow to split runs all its tiles at once)
-      lns_split = !lns_fx && comm_overlap && !m.p2p.on && (m.comm || m.local) && m.nranks > 1 && !want_res &&
-                  cs.cfg.isAdiabaticWall;
-      const bool lparts = T.nbi >= 2 + T.ne;
-      if (lns_fx) {
-        // the previous fused step's halo is still in the mailbox: this
-        // kernel's edge tiles copy it into the ghost columns they read
-        // (fx_ghost_prologue) instead of a separate unpack launch
-        // (valid whenever the mailbox's last publication was a fused lean
-        // N-S step: its parity stays untouched until this step publishes,
-        // so the copy is exact even if p2p_complete already unpacked it)
-        const ColList* Lg = nullptr;
-        if (lns_prev_valid && lns_ghost_prologue) {
-          Lg = lc_device(m.lns_pend);
-          if (Lg) {
-            lns_ghost_pending = false;
-            lns_pro_uses++;
-            lns_prologue_steps++;
-          }
-        }
-        p2p_complete();   // (a list new inside a capture: the separate unpack)
-        hipLaunchKernelGGL(kLnsFx[tv][want_res ? 1 : 0], dim3(ntile), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot,
-                           slot_next, serial, m.partials, fused_args(), Lc, Lg);
-        HIP_CHECK(hipGetLastError());
-        m.lns_pend = Lc;
-        lns_ghost_pending = lns_last_valid = true;   // unpacked by the next fused step or p2p_complete
-        if (lns_ghost_prologue) (void)lc_device(Lc);   // (uploaded now, outside any capture, when eager)
-        ghost_stale = true;   // lean representation in the ghosts
-        lns_fx_steps++;
-      } else if (lns_split) {
-        if (!m.comm_stream) {
-          HIP_CHECK(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
-          HIP_CHECK(hipEventCreateWithFlags(&m.ev_edge, hipEventDisableTiming));
-          HIP_CHECK(hipEventCreateWithFlags(&m.ev_halo, hipEventDisableTiming));
-        }
-        hipLaunchKernelGGL(lk, dim3(lparts ? (1 + T.ne) * T.nbj : ntile), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot,
-                           slot_next, serial, m.partials, lparts ? 1 : 0);
-      } else {
-        hipLaunchKernelGGL(lk, dim3(ntile), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot, slot_next, serial,
-                           m.partials, 0);
-      }
-      HIP_CHECK(hipGetLastError());
-      nres = (unsigned)ntile;
-      sbuf = 1 - sbuf;
-      pbuf = 1 - pbuf;
-      cbuf = 1 - cbuf;
-      dsbuf = 1 - dsbuf;
-      lns_steps++;
-      if (lns_split) {
-        HIP_CHECK(hipEventRecord(m.ev_edge, st));
-        // interior tiles in flight before the exchange is issued; they write
-        // neither the edge columns nor the ghost columns
-        if (lparts)
-          hipLaunchKernelGGL(lk, dim3((T.nbi - 1 - T.ne) * T.nbj), dim3(BLOCK), shmem, st, P, a, T, m.sc, slot,
-                             slot_next, serial, m.partials, 2);
-        HIP_CHECK(hipGetLastError());
-        if (m.local) {   // in-process group: the host orders the streams (see the inviscid path)
-          HIP_CHECK(hipEventSynchronize(m.ev_edge));
-          exchange(CpuSolver::HALO_LNS, -1, (void*)m.comm_stream);
-          HIP_CHECK(hipStreamSynchronize(m.comm_stream));
-        } else {
-          HIP_CHECK(hipStreamWaitEvent(m.comm_stream, m.ev_edge, 0));
-          exchange(CpuSolver::HALO_LNS, -1, (void*)m.comm_stream);
-          HIP_CHECK(hipEventRecord(m.ev_halo, m.comm_stream));
-          HIP_CHECK(hipStreamWaitEvent(st, m.ev_halo, 0));
-        }
-        exchange_dt(slot_next);
-        overlap_steps++;
-      }
-    }
-  } else {
-    if (lean_state) lean_materialize();
-    if (lns_state) lns_materialize();
-    step_split(P, want_res, slot, slot_next, serial, nblk, false);
+  const StepPath path = step_path(P);
+  // the ghost columns and dt of earlier fused steps, for every consumer but
+  // the fused kernels themselves (the tile kernel reads the mailbox; a fused
+  // lean N-S / mechanism step unpacks the previous fused step's halo itself)
+  const bool lns_fx_next = (path == StepPath::LeanMech || path == StepPath::LeanNs) && lns_state == 1 &&
+                           lean_state == 0 && m.p2p.on && p2p_fuse && m.nranks > 1;
+  if (path != StepPath::Tile) p2p_complete(lns_fx_next);
+  StepDone done{};
+  switch (path) {
+    case StepPath::Tile: done = step_tile(c); break;
+    case StepPath::LeanFlat: done = step_lean_flat(c); break;
+    case StepPath::FusedEuler: done = step_fused_euler(c); break;
+    case StepPath::LeanMech: done = lnm_step(c); break;
+    case StepPath::LeanNs: done = step_lean_ns(c); break;
+    case StepPath::Split:
+      if (lean_state) lean_materialize();
+      if (lns_state) lns_materialize();
+      done = step_split(c, false);
+      break;
   }
-  // new-state halo + global dt (MIN over ranks into the next slot)
-  if (fx_step) {
-    fx_pending = true;   // exchanged inside the tile kernel
-  } else if (lns_fx) {
-    lns_fx = false;   // exchanged inside the lean N-S kernel + unpacked
-  } else if (lnm_split) {
-    lnm_split = false;   // exchanged above, overlapped with the interior tiles
-  } else if (lns_split) {
-    lns_split = false;   // exchanged above, overlapped with the interior tiles
-  } else if ((m.comm || m.local || m.p2p.on) && m.nranks > 1) {
-    exchange(lns_state ? CpuSolver::HALO_LNS : lean_state ? CpuSolver::HALO_LEAN : CpuSolver::HALO_STATE, slot_next);
-  }
+  // new-state halo + global dt (MIN over ranks into the next slot), unless
+  // the step exchanged them itself (fused into its kernel, or overlapped
+  // with its interior tiles)
+  if (!done.exchanged && (m.comm || m.local || m.p2p.on) && m.nranks > 1)
+    exchange(lns_state ? CpuSolver::HALO_LNS : lean_state ? CpuSolver::HALO_LEAN : CpuSolver::HALO_STATE, c.slot_next);
   if (!cs.cfg.isAdiabaticWall) {
     SoA s = m.view(h, sbuf, abuf, dsbuf, pbuf);
-    hipLaunchKernelGGL(hf2d_wall_solid, dim3(nblk), dim3(BLOCK), 0, st, P, s, m.qdir, c0, c1);
+    hipLaunchKernelGGL(hf2d_wall_solid, dim3(c.nblk), dim3(BLOCK), 0, st, P, s, m.qdir, c.c0, c.c1);
     exchange(CpuSolver::HALO_QDIR);
-    hipLaunchKernelGGL(hf2d_wall_wall, dim3(nblk), dim3(BLOCK), 0, st, P, s, m.qdir, c0, c1, m.sc, slot);
+    hipLaunchKernelGGL(hf2d_wall_wall, dim3(c.nblk), dim3(BLOCK), 0, st, P, s, m.qdir, c.c0, c.c1, m.sc, c.slot);
     HIP_CHECK(hipGetLastError());
   }
   if (probe_cap) launch_probe_record(P);
@@ -4970,7 +4082,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   r.async = true;
   if (want_res) {
     hipLaunchKernelGGL(hf2d_reduce_residual, dim3(1), dim3(BLOCK), 0, st, m.partials,
-                       (long)nres * nres_waves, m.res_out);
+                       (long)done.nres * done.nres_waves, m.res_out);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(m.res_host, m.res_out, sizeof(ResidualPack), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));

@@ -153,7 +153,7 @@ class DeviceSolver : public SolverBase {
   bool dt_word_valid = false;
   // lean tile: skip stores of beta / CP whose bits did not change (HF2D_SKIP_SAME)
   bool tile_skip_same = false;
-  bool fx_step = false, fx_pending = false;
+  bool fx_pending = false;   // fused tile steps left the newest ghost columns and dt in the mailbox (p2p_complete)
   // fused lean N-S steps: the last step's halo is still in the mailbox; the
   // next fused step's edge tiles unpack it (lns_ghost_prologue, HF2D_GHOST_PROLOGUE)
   bool lns_ghost_pending = false, lns_ghost_prologue = true, lns_last_valid = false, lns_prev_valid = false;
@@ -182,9 +182,6 @@ class DeviceSolver : public SolverBase {
   // a separate read-back kernel after it (HF2D_HOST_TAIL=0: off)
   bool host_tail = true;
   bool lnm_overlap = false;   // mechanism step: edge tiles first, halo overlapped with the interior (opt-in)
-  bool lns_split = false;   // this lean N-S step ran edge-first with its halo overlapped
-  bool lnm_split = false;   // this lean mechanism step ran edge-first with its halo overlapped
-  bool lns_fx = false;      // this lean N-S step exchanged through the fused mailbox kernel
   long lns_fx_steps = 0;    // lean N-S steps with the fused xGMI mailbox exchange
   long p2p_mwg_exchanges = 0;   // mailbox exchanges through hf2d_p2p_push / hf2d_p2p_unpack
   long overlap_steps = 0;
@@ -318,11 +315,43 @@ class DeviceSolver : public SolverBase {
   void launch_stats(const StepParams& P);          // after it
   int post_step_view(SoA& s) const;                // PR_* kind and view both of them read
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)
-  void step_split(const StepParams& P, bool want_res, int slot, int slot_next, int serial, unsigned nblk, bool to_lns);
+  // One step (do_step_eager): the kernels that run it, what every path reads
+  // of the step, and what a path reports to the common tail.
+  enum class StepPath { Tile, LeanFlat, FusedEuler, LeanMech, LeanNs, Split };
+  struct StepCtx {
+    StepParams P;          // completed for this strip
+    bool want_res;
+    int slot, slot_next, serial;
+    unsigned nblk;         // workgroups of a one-cell-per-thread launch over the owned cells [c0, c1)
+    long c0, c1;
+    bool dt_word_ok;       // the previous step left the dt MIN in the slot's word
+    TileLast tile_prev;    // lean_tile_last of the previous step
+  };
+  struct StepDone {
+    unsigned nres;         // workgroups that wrote residual partials
+    int nres_waves;        // ... and partials per workgroup
+    bool exchanged;        // the new state's halo and the dt MIN are done (fused or overlapped)
+  };
+  StepPath step_path(const StepParams& P) const;   // (P completed: ny, sm)
+  StepDone step_tile(StepCtx& c);
+  StepDone step_lean_flat(const StepCtx& c);
+  StepDone step_fused_euler(const StepCtx& c);
+  StepDone step_lean_ns(const StepCtx& c);   // (with its entry step)
+  StepDone lnm_step(const StepCtx& c);       // (likewise)
+  StepDone step_split(const StepCtx& c, bool to_lns);
+  // edge-first steps of the host transports: the comm stream and its events;
+  // the edge part's halo (after ev_edge) on that stream, the dt MIN after it
+  void overlap_streams();
+  void overlap_exchange(int group, int slot_next);
+  // fused lean N-S / mechanism steps: the HALO_LNS list of the post-step
+  // buffers, and the previous step's list for the edge tiles' ghost prologue
+  // (nullptr: p2p_complete unpacks it)
+  void halo_fields_lns(std::vector<real*>& f, std::vector<unsigned char>& o, int sb, int pb, int cb, int ds) const;
+  struct ColList lns_post_list(const char* what) const;
+  const struct ColList* claim_ghost_prologue();
   bool lns_step_ok(const StepParams& P) const;
   bool lns_entry(const StepParams& P0) const;
   bool lnm_step_ok(const StepParams& P) const;
-  void lnm_step(const StepParams& P, bool want_res, int slot, int slot_next, int serial);
   void lnm_launch(const StepParams& P, const LnmArrays& a, const LeanTile& T, bool want_res, int slot, int slot_next,
                   int serial, unsigned ntile);
   // mechanism-mode kinetics of cells [k0, k1) (chem_fast / chem_mech / generic)

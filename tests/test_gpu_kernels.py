@@ -510,6 +510,34 @@ def test_comm_overlap_split_step_matches_single_gpu(gpu):
         np.testing.assert_array_equal(got[f], ref.field(f), err_msg=f)
 
 
+def test_comm_overlap_with_a_strip_too_narrow_to_split(gpu):
+    """Inviscid edge-first overlap beside a strip too narrow to split: two
+    97-column strips run edge tiles, halo, interior tiles, while the 20-column
+    strip (fewer than three tile columns, nbi < 3) runs all its tiles as the
+    edge launch with no interior launch -- the exchange sequence is the same
+    on every rank.  Bitwise equal to one GPU."""
+    text = decks.wedge15(214, 60, nmax=10 ** 6, nout=10 ** 5)
+    parts = [(0, 97), (97, 194), (194, 214)]
+    schedule = [(4, True), (13, False), (3, True)]
+    stats, lasts = {}, []
+
+    def hook(k, solvers):   # before the last chunk: the geometry of the overlapped steps
+        if k == 2:
+            lasts.extend(dict(s.lean_tile_last) for s in solvers)
+
+    got, summ = _virtual_ranks(gpu, text, 3, schedule, lean=True, stats=stats, parts=parts, chunk_hook=hook)
+    assert min(stats["overlap_steps"]) > 0, stats
+    assert lasts[0]["nt"] > 0 and lasts[0]["nbi"] >= 3, lasts
+    assert lasts[2]["nt"] > 0 and lasts[2]["nbi"] < 3, lasts
+    ref = gpu.Simulation(text, "gpu", lean=True)
+    for n, res in schedule:
+        ref.step(n, residual=res)
+    assert summ["dt"] == ref.summary()["dt"]
+    assert summ["time"] == ref.summary()["time"]
+    for f in FIELDS:
+        np.testing.assert_array_equal(got[f], ref.field(f), err_msg=f)
+
+
 # In-process ranks need a hardware queue each plus one (conftest sets
 # GPU_MAX_HW_QUEUES=16; test_p2p_import_refuses_too_few_queues covers the
 # guard); separate processes (the real deployment) have queues of their own.
