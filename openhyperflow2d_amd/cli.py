@@ -6,7 +6,8 @@
                                      [--profile FILE] [--fault-inject step:N,rank:R,kind:nan|kill]
                                      [--transport p2p|rccl]
                                      [--probe-history FILE.npz [--probe-capacity N]]
-                                     [--averages FILE.npz [--averages-every K]]
+                                     [--averages FILE.npz [--averages-every K] [--averages-favre]
+                                      [--averages-species all|A,B,...]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
   python -m openhyperflow2d_amd info deck.dat
   python -m openhyperflow2d_amd build
@@ -85,7 +86,10 @@ def _cmd_run(a) -> int:
             return 2
     if a.averages:
         try:
-            sim.start_averaging(every=a.averages_every)
+            sp = a.averages_species
+            if sp is not None and sp != "all":
+                sp = [s.strip() for s in sp.split(",") if s.strip()]
+            sim.start_averaging(every=a.averages_every, favre=a.averages_favre, species=sp)
         except (ValueError, RuntimeError) as e:
             print("--averages: %s" % e, file=sys.stderr, flush=True)
             return 2
@@ -113,9 +117,12 @@ def _cmd_run(a) -> int:
         from .models.simulation import PROBE_VARS
 
         av = sim.averages()
+        # (the keys of --averages-favre / --averages-species only when the flags were given)
+        extra = {k: np.asarray(av[k]) for k in ("species", "species_mean", "species_var", "favre_vars", "favre_mean",
+                                                 "favre_var", "favre_cov_uv", "favre_weight") if k in av}
         with open(a.averages, "wb") as f:   # (np.savez on a path would append ".npz")
             np.savez(f, mean=av["mean"], var=av["var"], cov_uv=av["cov_uv"], vars=np.asarray(PROBE_VARS),
-                     time=np.float64(av["time"]), samples=np.int64(av["samples"]))
+                     time=np.float64(av["time"]), samples=np.int64(av["samples"]), **extra)
         print("averages: %d samples over t = %.6e -> %s" % (av["samples"], av["time"], a.averages), flush=True)
     if rank == 0:
         sys.stdout.write(log)
@@ -217,6 +224,13 @@ def main(argv=None) -> int:
                         "samples to this file")
     r.add_argument("--averages-every", dest="averages_every", type=int, default=1, metavar="K",
                    help="sample every K-th step (default 1)")
+    r.add_argument("--averages-favre", dest="averages_favre", action="store_true",
+                   help="with --averages: also the density-weighted (Favre) means and variances of T, U, V and the "
+                        "listed species and the Favre U-V covariance (favre_vars / favre_mean / favre_var / "
+                        "favre_cov_uv / favre_weight)")
+    r.add_argument("--averages-species", dest="averages_species", metavar="all|A,B,...",
+                   help="with --averages, mechanism decks only: also the mean and variance of these species' mass "
+                        "fractions (species / species_mean / species_var)")
     d = sub.add_parser("deck", help="write a generated deck")
     d.add_argument("name")
     d.add_argument("--nx", type=int)

@@ -656,9 +656,10 @@ PYBIND11_MODULE(_hf2d, m) {
            })
       .def("clear_probe_history", &SolverBase::clear_probe_history)
       .def("start_averaging", &SolverBase::start_averaging, py::arg("every") = 1, py::arg("second_moments") = true,
-           py::arg("step_weight") = false,
+           py::arg("step_weight") = false, py::arg("favre") = false, py::arg("species") = std::vector<int>{},
            "arm the whole-field accumulator: weighted running mean (and variances, U-V covariance) of "
-           "(p, T, rho, U, V) over every `every`-th step")
+           "(p, T, rho, U, V) over every `every`-th step; favre: the density-weighted means of T, U, V and the "
+           "listed species as well; species: mechanism indices whose mass fractions are averaged")
       .def("reset_averaging", &SolverBase::reset_averaging)
       .def("stop_averaging", &SolverBase::stop_averaging)
       .def("averages",
@@ -680,6 +681,32 @@ PYBIND11_MODULE(_hf2d, m) {
                std::copy(A.cov_uv.begin(), A.cov_uv.end(), cov.mutable_data());
                d["var"] = var;
                d["cov_uv"] = cov;
+             }
+             // the favre / species options: keys only for what was armed
+             auto put = [&](const char* key, const std::vector<double>& v, py::ssize_t np) {
+               py::array_t<double> a(np < 0 ? std::vector<py::ssize_t>{nxl, ny} : std::vector<py::ssize_t>{np, nxl, ny});
+               std::copy(v.begin(), v.end(), a.mutable_data());
+               d[key] = a;
+             };
+             const py::ssize_t ns = (py::ssize_t)A.species.size();
+             py::list names;
+             for (int q : A.species) names.append(s.cs.cfg.mech->species.at((size_t)q));
+             if (ns > 0) {
+               d["species"] = py::tuple(names);
+               put("species_mean", A.species_mean, ns);
+               if (A.second_moments) put("species_var", A.species_var, ns);
+             }
+             if (A.favre) {
+               py::list fv;
+               for (const char* v : {"T", "U", "V"}) fv.append(v);
+               for (auto n : names) fv.append(py::str("Y:") + py::str(n));
+               d["favre_vars"] = py::tuple(fv);
+               put("favre_mean", A.favre_mean, 3 + ns);
+               put("favre_weight", A.favre_weight, -1);
+               if (A.second_moments) {
+                 put("favre_var", A.favre_var, 3 + ns);
+                 put("favre_cov_uv", A.favre_cov_uv, -1);
+               }
              }
              d["time"] = A.time;
              d["samples"] = A.samples;

@@ -68,4 +68,115 @@ HF_HD inline void stats_cell(double w, double r, const real* row, double* m, dou
   if (MOMENTS) C[0] = C[0] + (w * dU) * eV;
 }
 
+// Extension (start_averaging's favre / species options): mass fractions of
+// listed mechanism species and Favre (density-weighted) averages.  With w, r
+// the tick's values of this sample and rho = row[2]:
+//   species, for each listed s in list order, Y_s = rho != 0 ? rhoY_s / rho : 0
+//   (the division field("Y:<s>") performs on the post-step partial density):
+//     d = Y_s - mY_s;  mY_s := mY_s + r * d;  e = Y_s - mY_s
+//     MY_s := MY_s + (w * d) * e
+//   Favre, per cell with its own weight sum G:
+//     om = w * rho;  G1 = G + om;  q = G1 > 0 ? om / G1 : 0;  G := G1
+//     for x in (T, U, V, Y_s...):
+//       d = x - f_x;  f_x := f_x + q * d;  e = x - f_x;  F_x := F_x + (om * d) * e
+//     CF := CF + (om * d_U) * e_V
+// in double, in this order, without contraction.  species_var = MY / W,
+// favre_var = F / G and favre_cov_uv = CF / G (0 where G == 0) are formed by
+// the reader.  Every plane depends on its own history only, so the species and
+// the Favre update of Y_s share one pass over the list.
+constexpr int STATS_MAX_SPECIES = 16;
+constexpr int STATS_FAVRE_BASE = 3;   // T, U, V; the listed species follow
+
+struct StatsExt {
+  int ns = 0;                      // listed species
+  int sp[STATS_MAX_SPECIES] = {};  // their mechanism indices
+  double* mY = nullptr;   // [ns][N] mass-fraction means
+  double* MY = nullptr;   // [ns][N] weighted squared deviations (second moments only)
+  double* G = nullptr;    // [N] Favre weight sum
+  double* f = nullptr;    // [3 + ns][N] Favre means
+  double* F = nullptr;    // [3 + ns][N] Favre squared deviations (second moments only)
+  double* CF = nullptr;   // [N] Favre U, V co-moment (second moments only)
+};
+
+// Planes of N doubles one accumulator holds (base, species, Favre).
+inline size_t stats_plane_count(bool second_moments, bool favre, int ns) {
+  size_t n = second_moments ? 2 * STATS_VARS + 1 : STATS_VARS;
+  n += (size_t)ns * (second_moments ? 2 : 1);
+  if (favre) n += 1 + (size_t)(STATS_FAVRE_BASE + ns) * (second_moments ? 2 : 1) + (second_moments ? 1 : 0);
+  return n;
+}
+
+// The extension's pointers into one block of stats_plane_count planes that
+// starts with the base planes.
+inline void stats_ext_planes(StatsExt& x, double* base, size_t N, bool second_moments, bool favre) {
+  double* p = base + (second_moments ? 2 * STATS_VARS + 1 : STATS_VARS) * N;
+  auto take = [&](bool on, size_t n) {
+    double* q = on && n ? p : nullptr;
+    if (on) p += n * N;
+    return q;
+  };
+  const size_t ns = (size_t)x.ns;
+  x.mY = take(true, ns);
+  x.MY = take(second_moments, ns);
+  x.G = take(favre, 1);
+  x.f = take(favre, STATS_FAVRE_BASE + ns);
+  x.F = take(favre && second_moments, STATS_FAVRE_BASE + ns);
+  x.CF = take(favre && second_moments, 1);
+}
+
+// One cell: row as stats_cell; Ys the cell's entry of the species block
+// [nsp][N] of post-step partial densities; x's planes are indexed with c.
+template <bool MOMENTS, bool FAVRE>
+HF_HD inline void stats_cell_x(double w, double r, const real* row, const real* Ys, long N, const StatsExt& x, long c) {
+  const double rho = (double)row[2];
+  double om = 0.0, q = 0.0, dU = 0.0, eV = 0.0;
+  if (FAVRE) {
+    om = w * rho;
+    const double G1 = x.G[c] + om;
+    q = G1 > 0.0 ? om / G1 : 0.0;
+    x.G[c] = G1;
+#pragma unroll
+    for (int k = 0; k < STATS_FAVRE_BASE; k++) {
+      const double v = (double)row[k == 0 ? 1 : k + 2];   // T, U, V
+      const long o = (long)k * N + c;
+      const double f0 = x.f[o];
+      const double d = v - f0;
+      const double f1 = f0 + q * d;
+      x.f[o] = f1;
+      if (MOMENTS) {
+        const double e = v - f1;
+        x.F[o] = x.F[o] + (om * d) * e;
+        if (k == 1) dU = d;
+        if (k == 2) eV = e;
+      }
+    }
+    if (MOMENTS) x.CF[c] = x.CF[c] + (om * dU) * eV;
+  }
+  for (int s = 0; s < x.ns; s++) {
+    const double Y = rho != 0.0 ? (double)Ys[(long)x.sp[s] * N] / rho : 0.0;
+    const long o = (long)s * N + c;
+    {
+      const double m0 = x.mY[o];
+      const double d = Y - m0;
+      const double m1 = m0 + r * d;
+      x.mY[o] = m1;
+      if (MOMENTS) {
+        const double e = Y - m1;
+        x.MY[o] = x.MY[o] + (w * d) * e;
+      }
+    }
+    if (FAVRE) {
+      const long of = o + (long)STATS_FAVRE_BASE * N;
+      const double f0 = x.f[of];
+      const double d = Y - f0;
+      const double f1 = f0 + q * d;
+      x.f[of] = f1;
+      if (MOMENTS) {
+        const double e = Y - f1;
+        x.F[of] = x.F[of] + (om * d) * e;
+      }
+    }
+  }
+}
+
 }  // namespace hf2d

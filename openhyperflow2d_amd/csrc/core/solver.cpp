@@ -451,8 +451,24 @@ void SolverBase::record_probes(const std::vector<std::pair<int, int>>&, long) {
 ProbeHistory SolverBase::probe_history() { throw std::runtime_error("this backend has no per-step probe recorder"); }
 void SolverBase::clear_probe_history() {}
 
-void SolverBase::start_averaging(int, bool, bool) {
+void SolverBase::start_averaging(int, bool, bool, bool, const std::vector<int>&) {
   throw std::runtime_error("this backend has no flow-statistics accumulator");
+}
+void SolverBase::check_averaging(int every, const std::vector<int>& species, int nsp) {
+  if (every < 1) throw std::invalid_argument("start_averaging: every must be at least 1");
+  if (species.empty()) return;
+  if (nsp <= 0) throw std::invalid_argument("start_averaging: species statistics need a deck in mechanism mode");
+  if ((int)species.size() > STATS_MAX_SPECIES)
+    throw std::invalid_argument("start_averaging: " + std::to_string(species.size()) + " species, at most " +
+                                std::to_string(STATS_MAX_SPECIES));
+  for (size_t k = 0; k < species.size(); k++) {
+    if (species[k] < 0 || species[k] >= nsp)
+      throw std::invalid_argument("start_averaging: species index " + std::to_string(species[k]) + " outside the mechanism's " +
+                                  std::to_string(nsp));
+    for (size_t q = 0; q < k; q++)
+      if (species[q] == species[k])
+        throw std::invalid_argument("start_averaging: species index " + std::to_string(species[k]) + " listed twice");
+  }
 }
 void SolverBase::reset_averaging() {}
 void SolverBase::stop_averaging() {}
@@ -834,22 +850,27 @@ void CpuSolver::clear_probe_history() { probe_total = 0; }
 
 // the values download() would put into the records now: the lean inviscid
 // state keeps its pressure in P2 (lean_materialize_cell copies it to p)
-void CpuSolver::start_averaging(int every, bool second_moments, bool step_weight) {
-  if (every < 1) throw std::invalid_argument("start_averaging: every must be at least 1");
+void CpuSolver::start_averaging(int every, bool second_moments, bool step_weight, bool favre,
+                                const std::vector<int>& species) {
+  check_averaging(every, species, h.nsp);
   avg_sc = StatsScalars{};
   avg_sc.every = every;
   avg_sc.step_weight = step_weight ? 1 : 0;
   avg_second = second_moments;
-  avg_m.assign((size_t)STATS_VARS * h.N, 0.0);
-  avg_M.assign(second_moments ? (size_t)STATS_VARS * h.N : 0, 0.0);
-  avg_C.assign(second_moments ? (size_t)h.N : 0, 0.0);
+  avg_favre = favre;
+  avg_x = StatsExt{};
+  avg_x.ns = (int)species.size();
+  std::copy(species.begin(), species.end(), avg_x.sp);
+  avg_m.assign(stats_plane_count(second_moments, favre, avg_x.ns) * (size_t)h.N, 0.0);
+  stats_ext_planes(avg_x, avg_m.data(), (size_t)h.N, second_moments, favre);
   avg_sc.t_seen = (double)(cs.global_time + cur_time_part);
   avg_on = avg_armed = true;
 }
 
 void CpuSolver::reset_averaging() {
   if (!avg_on) return;
-  start_averaging(avg_sc.every, avg_second, avg_sc.step_weight != 0);
+  start_averaging(avg_sc.every, avg_second, avg_sc.step_weight != 0, avg_favre,
+                  std::vector<int>(avg_x.sp, avg_x.sp + avg_x.ns));
 }
 
 void CpuSolver::stop_averaging() { avg_on = false; }
@@ -863,15 +884,28 @@ FlowAverages CpuSolver::averages() {
   A.second_moments = avg_second;
   A.time = avg_sc.W;
   A.samples = (long)avg_sc.samples;
+  A.favre = avg_favre;
+  A.species.assign(avg_x.sp, avg_x.sp + avg_x.ns);
   const long c0 = (long)l_off * h.ny, n = (long)(gi1 - gi0) * h.ny;
-  auto planes = [&](const std::vector<double>& src, int np, std::vector<double>& dst) {
+  auto planes = [&](const double* src, int np, std::vector<double>& dst) {
     dst.resize((size_t)np * n);
-    for (int k = 0; k < np; k++) std::copy(src.begin() + k * h.N + c0, src.begin() + k * h.N + c0 + n, dst.begin() + k * n);
+    for (int k = 0; k < np; k++) std::copy(src + k * h.N + c0, src + k * h.N + c0 + n, dst.begin() + k * n);
   };
-  planes(avg_m, STATS_VARS, A.mean);
+  const int ns = avg_x.ns, nf = STATS_FAVRE_BASE + ns;
+  planes(avg_m.data(), STATS_VARS, A.mean);
+  planes(avg_x.mY, ns, A.species_mean);
+  if (avg_favre) {
+    planes(avg_x.G, 1, A.favre_weight);
+    planes(avg_x.f, nf, A.favre_mean);
+  }
   if (avg_second) {
-    planes(avg_M, STATS_VARS, A.var);
-    planes(avg_C, 1, A.cov_uv);
+    planes(avg_m.data() + (size_t)STATS_VARS * h.N, STATS_VARS, A.var);
+    planes(avg_m.data() + 2 * (size_t)STATS_VARS * h.N, 1, A.cov_uv);
+    planes(avg_x.MY, ns, A.species_var);
+    if (avg_favre) {
+      planes(avg_x.F, nf, A.favre_var);
+      planes(avg_x.CF, 1, A.favre_cov_uv);
+    }
     A.finish(avg_sc.W);
   }
   return A;
@@ -881,13 +915,27 @@ void CpuSolver::after_step() {
   if (avg_on && stats_tick(avg_sc, (double)(cs.global_time + cur_time_part))) {
     const real* p = lean_state ? P2[pbuf].data() : h.p.data();
     const long c0 = (long)l_off * h.ny, c1 = c0 + (long)(gi1 - gi0) * h.ny;
+    const bool ext = avg_favre || avg_x.ns > 0;
+    const real* Ys = avg_x.ns > 0 ? h.Ys[0].data() : nullptr;   // post-step partial densities (download reads them)
+    double* const M = avg_m.data() + (size_t)STATS_VARS * h.N;
+    double* const C = M + (size_t)STATS_VARS * h.N;
+    const double w = avg_sc.w, rr = avg_sc.r;
     for (long c = c0; c < c1; c++) {
       if (has_all(h.CT[c], CT_SOLID) || !has_all(h.CT[c], CT_NODE_IS_SET)) continue;
       const real row[STATS_VARS] = {p[c], h.Tg[pbuf][c], h.S[0][c], h.U[pbuf][c], h.V[pbuf][c]};
       if (avg_second)
-        stats_cell<true>(avg_sc.w, avg_sc.r, row, &avg_m[c], &avg_M[c], &avg_C[c], h.N);
+        stats_cell<true>(w, rr, row, &avg_m[c], M + c, C + c, h.N);
       else
-        stats_cell<false>(avg_sc.w, avg_sc.r, row, &avg_m[c], nullptr, nullptr, h.N);
+        stats_cell<false>(w, rr, row, &avg_m[c], nullptr, nullptr, h.N);
+      if (!ext) continue;
+      const real* yc = Ys ? Ys + c : nullptr;
+      if (avg_second) {
+        if (avg_favre) stats_cell_x<true, true>(w, rr, row, yc, h.N, avg_x, c);
+        else stats_cell_x<true, false>(w, rr, row, yc, h.N, avg_x, c);
+      } else {
+        if (avg_favre) stats_cell_x<false, true>(w, rr, row, yc, h.N, avg_x, c);
+        else stats_cell_x<false, false>(w, rr, row, yc, h.N, avg_x, c);
+      }
     }
   }
   if (probe_cap == 0) return;

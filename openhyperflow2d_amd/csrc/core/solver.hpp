@@ -107,11 +107,31 @@ struct FlowAverages {
   std::vector<double> mean;      // [STATS_VARS][nxl][ny]
   std::vector<double> var;       // [STATS_VARS][nxl][ny]  M / W (second moments only)
   std::vector<double> cov_uv;    // [nxl][ny]              C / W (second moments only)
-  // M, C -> var, cov_uv: the IEEE division by W (0 before the first sample)
+  // the favre / species options (only what was armed is filled)
+  bool favre = false;
+  std::vector<int> species;           // mechanism indices of the listed species, in list order
+  std::vector<double> species_mean;   // [ns][nxl][ny]
+  std::vector<double> species_var;    // [ns][nxl][ny]      MY / W (second moments only)
+  std::vector<double> favre_weight;   // [nxl][ny]          G
+  std::vector<double> favre_mean;     // [3 + ns][nxl][ny]  T, U, V, the listed species
+  std::vector<double> favre_var;      // [3 + ns][nxl][ny]  F / G (second moments only)
+  std::vector<double> favre_cov_uv;   // [nxl][ny]          CF / G (second moments only)
+  // M, C -> var, cov_uv: the IEEE division by W (0 before the first sample);
+  // the Favre moments by the cell's own weight sum G (0 where G == 0)
   void finish(double W) {
+    const size_t n = favre_weight.size();
+    for (size_t k = 0; k < favre_var.size(); k++) {
+      const double G = favre_weight[k % n];
+      favre_var[k] = G != 0.0 ? favre_var[k] / G : 0.0;
+    }
+    for (size_t k = 0; k < favre_cov_uv.size(); k++) {
+      const double G = favre_weight[k];
+      favre_cov_uv[k] = G != 0.0 ? favre_cov_uv[k] / G : 0.0;
+    }
     if (!(W > 0.0)) return;
     for (double& x : var) x = x / W;
     for (double& x : cov_uv) x = x / W;
+    for (double& x : species_var) x = x / W;
   }
 };
 
@@ -209,12 +229,19 @@ class SolverBase {
   // time since the previous sample (step_weight: 1).  Starting again, also
   // with other options, restarts from zero; reset keeps the options; stop
   // freezes the result, which averages() still returns.
-  // std::invalid_argument: every < 1.  std::runtime_error: averages() before
-  // any start, or a backend without an accumulator.
-  virtual void start_averaging(int every, bool second_moments, bool step_weight);
+  // favre: the density-weighted means of T, U, V and the listed species
+  // (variances, u''v'') with the cell's own weight sum; species: mechanism
+  // indices whose mass fractions rhoY_s / rho are averaged as well (mechanism
+  // mode only, at most STATS_MAX_SPECIES, none twice).
+  // std::invalid_argument: every < 1 or a bad species list.  std::runtime_error:
+  // averages() before any start, or a backend without an accumulator.
+  virtual void start_averaging(int every, bool second_moments, bool step_weight, bool favre = false,
+                               const std::vector<int>& species = {});
   virtual void reset_averaging();
   virtual void stop_averaging();
   virtual FlowAverages averages();
+  // start_averaging's argument check (nsp: the backend's mechanism species, 0 outside mechanism mode)
+  static void check_averaging(int every, const std::vector<int>& species, int nsp);
 
  protected:
   // called by advance() after a step the host completed (not the device's asynchronous ones)
@@ -263,13 +290,16 @@ class CpuSolver : public SolverBase {
   std::vector<real> probe_rows;     // [probe_cap][nprobes][PROBE_HISTORY_VARS]
   std::vector<double> probe_times;  // [probe_cap]
   // host accumulator: the arrays the probe recorder reads, after each step
-  void start_averaging(int every, bool second_moments, bool step_weight) override;
+  void start_averaging(int every, bool second_moments, bool step_weight, bool favre = false,
+                       const std::vector<int>& species = {}) override;
   void reset_averaging() override;
   void stop_averaging() override;
   FlowAverages averages() override;
   StatsScalars avg_sc;
   bool avg_on = false, avg_armed = false, avg_second = false;   // armed: planes exist (on, or stopped)
-  std::vector<double> avg_m, avg_M, avg_C;   // [STATS_VARS][N], [STATS_VARS][N], [N]
+  bool avg_favre = false;
+  std::vector<double> avg_m;   // every plane (stats_plane_count): m [STATS_VARS][N], M [STATS_VARS][N], C [N], then avg_x's
+  StatsExt avg_x;              // species list and the extension's planes inside avg_m
 
   HostArrays h;
   int gi0, gi1;     // owned global columns

@@ -1215,6 +1215,8 @@ struct DeviceSolver::Impl {
   ProbeRing ring{};            // per-step recorder (record_probes); cap == 0: not armed
   FlowStats stats{};           // whole-field statistics (start_averaging)
   size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
+  size_t stats_used = 0;       // of which the armed options use (stats_plane_count)
+  StatsExt stats_x{};          // species list and the favre / species planes inside them
   DevScalars* sc = nullptr;
   DevScalars* sc_host = nullptr;   // pinned
   bool sc_kernel = true;           // sync_scalars: hf2d_scalars_out instead of a copy (HF2D_SC_KERNEL=0: copy)
@@ -2164,6 +2166,10 @@ int DeviceSolver::post_step_view(SoA& s) const {
       s.kk = kkx[cbuf];          // the lagged k of fill_node's skip test
       s.Tg = m.Tst[1 - cbuf];    // stored state of the new level
       s.p = px[1 - cbuf];
+      // the post-kinetics species of Sp^{m+1} (lnm_arrays: Ys[sb] beside
+      // S[1 - sb]), which lns_materialize leaves where they are and download()
+      // reads; the other paths' view holds Ys[sbuf] already
+      s.Ys = m.Ys[sbuf];
     } else {
       kind = sk_mode == SK_SGT ? PR_SGT : PR_SGL;
       s.CP = cpx[1 - cbuf];
@@ -2200,13 +2206,14 @@ void DeviceSolver::launch_probe_record(const StepParams& P) {
 // ---------------------------------------------------------------------------
 // Whole-field time averages (hip/flow_stats.hpp)
 // ---------------------------------------------------------------------------
-void DeviceSolver::start_averaging(int every, bool second_moments, bool step_weight) {
-  if (every < 1) throw std::invalid_argument("start_averaging: every must be at least 1");
+void DeviceSolver::start_averaging(int every, bool second_moments, bool step_weight, bool favre,
+                                   const std::vector<int>& species) {
+  check_averaging(every, species, h.nsp);
   flush_pending();
   p2p_complete();
   HIP_CHECK(hipSetDevice(dev));
   Impl& m = *impl;
-  const size_t N = (size_t)h.N, planes = second_moments ? 2 * STATS_VARS + 1 : STATS_VARS;
+  const size_t N = (size_t)h.N, planes = stats_plane_count(second_moments, favre, (int)species.size());
   FlowStats f = m.stats;
   if (planes > m.stats_planes) {   // (arming again with as many planes or fewer reuses them)
     f.m = m.mem.alloc<double>(planes * N);
@@ -2217,6 +2224,10 @@ void DeviceSolver::start_averaging(int every, bool second_moments, bool step_wei
   f.C = second_moments ? f.m + 2 * STATS_VARS * N : nullptr;
   f.c0 = (long)l_off * h.ny;
   f.c1 = f.c0 + (long)(gi1 - gi0) * h.ny;
+  StatsExt x{};
+  x.ns = (int)species.size();
+  std::copy(species.begin(), species.end(), x.sp);
+  stats_ext_planes(x, f.m, N, second_moments, favre);
   HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
   StatsScalars s0{};
   s0.every = every;
@@ -2228,7 +2239,11 @@ void DeviceSolver::start_averaging(int every, bool second_moments, bool step_wei
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(m.stream));
   m.stats = f;
+  m.stats_x = x;
+  m.stats_used = planes;
   stats_second = second_moments;
+  stats_favre = favre;
+  stats_species = species;
   stats_on = stats_armed = true;
   stats_gen++;   // windows captured so far must not replay (mode_signature)
 }
@@ -2237,8 +2252,7 @@ void DeviceSolver::reset_averaging() {
   if (!stats_on) return;
   flush_pending();
   Impl& m = *impl;
-  const size_t planes = stats_second ? 2 * STATS_VARS + 1 : STATS_VARS;
-  HIP_CHECK(hipMemsetAsync(m.stats.m, 0, planes * (size_t)h.N * sizeof(double), m.stream));
+  HIP_CHECK(hipMemsetAsync(m.stats.m, 0, m.stats_used * (size_t)h.N * sizeof(double), m.stream));
   hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, m.stats.sc, m.sc);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(m.stream));
@@ -2257,11 +2271,14 @@ FlowAverages DeviceSolver::averages() {
   HIP_CHECK(hipSetDevice(dev));
   Impl& m = *impl;
   const FlowStats& f = m.stats;
+  const StatsExt& x = m.stats_x;
   FlowAverages A;
   A.gi0 = gi0;
   A.gi1 = gi1;
   A.ny = h.ny;
   A.second_moments = stats_second;
+  A.favre = stats_favre;
+  A.species = stats_species;
   const size_t n = (size_t)(f.c1 - f.c0), N = (size_t)h.N;
   StatsScalars sc;
   HIP_CHECK(hipMemcpyAsync(&sc, f.sc, sizeof sc, hipMemcpyDeviceToHost, m.stream));
@@ -2271,10 +2288,21 @@ FlowAverages DeviceSolver::averages() {
       HIP_CHECK(hipMemcpyAsync(dst.data() + k * n, src + k * N + f.c0, n * sizeof(double), hipMemcpyDeviceToHost,
                                m.stream));
   };
+  const int ns = x.ns, nf = STATS_FAVRE_BASE + ns;
   planes(f.m, STATS_VARS, A.mean);
+  planes(x.mY, ns, A.species_mean);
+  if (stats_favre) {
+    planes(x.G, 1, A.favre_weight);
+    planes(x.f, nf, A.favre_mean);
+  }
   if (stats_second) {
     planes(f.M, STATS_VARS, A.var);
     planes(f.C, 1, A.cov_uv);
+    planes(x.MY, ns, A.species_var);
+    if (stats_favre) {
+      planes(x.F, nf, A.favre_var);
+      planes(x.CF, 1, A.favre_cov_uv);
+    }
   }
   HIP_CHECK(hipStreamSynchronize(m.stream));
   A.time = sc.W;
@@ -2295,6 +2323,21 @@ static void launch_stats_kind(hipStream_t st, unsigned nblk, bool second, const 
     hipLaunchKernelGGL((hf2d_stats_accum<KIND, false>), dim3(nblk), dim3(STATS_BLOCK), 0, st, P, s, f);
 }
 
+// the same pass with Favre averages or species statistics armed
+template <int KIND>
+static void launch_stats_x_kind(hipStream_t st, unsigned nblk, bool second, bool favre, const StepParams& P,
+                                const SoA& s, const FlowStats& f, const StatsExt& x) {
+  const dim3 g(nblk), b(STATS_BLOCK);
+  if (second && favre)
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, true, true>), g, b, 0, st, P, s, f, x);
+  else if (second)
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, true, false>), g, b, 0, st, P, s, f, x);
+  else if (favre)
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, false, true>), g, b, 0, st, P, s, f, x);
+  else
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, false, false>), g, b, 0, st, P, s, f, x);
+}
+
 void DeviceSolver::launch_stats(const StepParams& P) {
   Impl& m = *impl;
   SoA s;
@@ -2303,6 +2346,20 @@ void DeviceSolver::launch_stats(const StepParams& P) {
   hipLaunchKernelGGL(hf2d_stats_tick, dim3(1), dim3(64), 0, m.stream, f.sc, m.sc);
   HIP_CHECK(hipGetLastError());
   const unsigned nblk = (unsigned)((f.c1 - f.c0 + STATS_BLOCK - 1) / STATS_BLOCK);
+  if (stats_favre || m.stats_x.ns > 0) {
+    const StatsExt& x = m.stats_x;
+    // (a listed species is a plane of the view's block: check_averaging)
+    if (x.ns > 0 && (!s.Ys || s.nsp != h.nsp)) throw std::runtime_error("flow statistics: the step's view holds no species block");
+    switch (kind) {
+      case PR_SGL: launch_stats_x_kind<PR_SGL>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      case PR_SGT: launch_stats_x_kind<PR_SGT>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      case PR_MECH: launch_stats_x_kind<PR_MECH>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      case PR_LEAN: launch_stats_x_kind<PR_LEAN>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      default: launch_stats_x_kind<PR_GATHER>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   switch (kind) {
     case PR_SGL: launch_stats_kind<PR_SGL>(m.stream, nblk, stats_second, P, s, f); break;
     case PR_SGT: launch_stats_kind<PR_SGT>(m.stream, nblk, stats_second, P, s, f); break;

@@ -110,13 +110,17 @@ class DeviceSolver : public SolverBase {
   // whole-field statistics (hip/flow_stats.hpp): hf2d_stats_tick and
   // hf2d_stats_accum follow the recorder's launch while armed; reading the
   // averages neither leaves the lean state nor changes a ping-pong parity
-  void start_averaging(int every, bool second_moments, bool step_weight) override;
+  // (with favre or species armed hf2d_stats_accum_x takes the cell pass)
+  void start_averaging(int every, bool second_moments, bool step_weight, bool favre = false,
+                       const std::vector<int>& species = {}) override;
   void reset_averaging() override;
   void stop_averaging() override;
   FlowAverages averages() override;
   bool stats_on = false;        // the two kernels are launched
   bool stats_armed = false;     // planes exist (on, or stopped: averages() reads the frozen result)
   bool stats_second = false;
+  bool stats_favre = false;
+  std::vector<int> stats_species;   // mechanism indices of the listed species
   int stats_gen = 0;            // arming generation (mode_signature, as probe_gen)
   bool lean_T_stored = true;    // the last lean inviscid step stored T (every kernel but the plain tile variant)
   void trace_push(const char* name) override;

@@ -7,6 +7,8 @@
 //                      through probe_row<KIND> (probe_history.hpp), i.e. bit for
 //                      bit what a download after the step yields, folded into
 //                      the double planes m, M, C
+//   hf2d_stats_accum_x the same pass when Favre averages or species statistics
+//                      are armed: the base planes, then stats_cell_x's
 // Both run on the solver's stream after the step's last kernel, so they are
 // captured into the step graphs.  The tick is a kernel of its own, not the tail
 // of the cell pass: w and r are then the product of an earlier launch which
@@ -62,6 +64,30 @@ __global__ __launch_bounds__(STATS_BLOCK) void hf2d_stats_accum(StepParams P, So
   real row[PROBE_VARS];
   probe_row<KIND>(P, s, idx, row);
   stats_cell<MOMENTS>(f.sc->w, f.sc->r, row, f.m + idx, f.M + idx, f.C + idx, s.N);
+}
+
+// The cell pass with the favre / species options armed (stats_cell_x), in
+// place of hf2d_stats_accum: the same lane-per-cell layout and the same row,
+// evaluated once, then the base planes and the extension's.  The listed
+// species' post-step partial densities are s.Ys (post_step_view); their
+// indices and the plane pointers travel in x, so the species loop's trip count
+// and plane offsets are wave-uniform.  Every plane is read and written once
+// per sample, consecutive lanes on consecutive doubles: 16 B per plane and
+// cell-sample, HBM-bound like the base pass.
+static_assert(sizeof(StepParams) + sizeof(SoA) + sizeof(FlowStats) + sizeof(StatsExt) + 32 <= 4096,
+              "kernel-argument segment");
+template <int KIND, bool MOMENTS, bool FAVRE>
+__global__ __launch_bounds__(STATS_BLOCK) void hf2d_stats_accum_x(StepParams P, SoA s, FlowStats f, StatsExt x) {
+  if (!f.sc->sample) return;
+  const long idx = f.c0 + (long)blockIdx.x * STATS_BLOCK + (long)threadIdx.x;
+  if (idx >= f.c1) return;
+  const u64 ct = s.CT[idx];
+  if (has_all(ct, CT_SOLID) || !has_all(ct, CT_NODE_IS_SET)) return;
+  real row[PROBE_VARS];
+  probe_row<KIND>(P, s, idx, row);
+  const double w = f.sc->w, r = f.sc->r;
+  stats_cell<MOMENTS>(w, r, row, f.m + idx, f.M + idx, f.C + idx, s.N);
+  stats_cell_x<MOMENTS, FAVRE>(w, r, row, s.Ys + idx, s.N, x, idx);
 }
 #endif
 

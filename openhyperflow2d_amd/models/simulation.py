@@ -136,7 +136,8 @@ class Simulation:
         self.solver.clear_probe_history()
 
     # -- time-averaged flow statistics ---------------------------------------
-    def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time") -> None:
+    def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time",
+                        favre: bool = False, species=None) -> None:
         """Arm the whole-field accumulator.
 
         From now on every ``every``-th step (the first one ``every`` steps
@@ -155,12 +156,61 @@ class Simulation:
         of every k-th state; ``weight="step"`` uses ``w = 1``.  On the GPU two
         small kernels run at the end of each step, inside the step graphs, and
         the lean states are never materialised.  Starting again restarts from
-        zero.  ``ValueError``: ``every < 1`` or an unknown ``weight``."""
+        zero.
+
+        ``species`` (mechanism mode only): ``"all"`` or a sequence of species
+        names whose mass fractions are averaged too.  With ``rho`` the row's
+        density and ``rhoY_s`` the post-step partial density, for each listed
+        species in list order::
+
+            Y_s = rho != 0 ? rhoY_s / rho : 0          (what field("Y:<s>") returns)
+            d = Y_s - mY_s;  mY_s = mY_s + r * d;  e = Y_s - mY_s
+            MY_s = MY_s + (w * d) * e
+
+        ``favre=True`` adds the density-weighted (Favre) averages of ``T, U, V``
+        and the listed species, per cell with its own weight sum ``G``::
+
+            om = w * rho;  G1 = G + om;  q = G1 > 0 ? om / G1 : 0;  G = G1
+            for x in (T, U, V, Y_s...):
+                d = x - f_x;  f_x = f_x + q * d;  e = x - f_x;  F_x = F_x + (om * d) * e
+            CF = CF + (om * d_U) * e_V
+
+        A call without the two options launches the same kernels and returns
+        the same keys as before.  ``ValueError``: ``every < 1``, an unknown
+        ``weight``, species on a deck that is not in mechanism mode, an unknown
+        or repeated species name, an empty list, or more than 16 species."""
         if weight not in ("time", "step"):
             raise ValueError("start_averaging: weight must be 'time' or 'step', not %r" % (weight,))
         if int(every) < 1:
             raise ValueError("start_averaging: every must be at least 1")
-        self.solver.start_averaging(int(every), bool(second_moments), weight == "step")
+        idx = self._species_indices(species)
+        self.solver.start_averaging(int(every), bool(second_moments), weight == "step", bool(favre), idx)
+
+    def _species_indices(self, species) -> list:
+        """start_averaging's ``species`` -> mechanism indices (``None``: none)."""
+        if species is None:
+            return []
+        if not self.case.mech_mode:
+            raise ValueError("start_averaging: species statistics need a deck in mechanism mode")
+        names = list(self.case.mech_species)
+        if isinstance(species, str):
+            if species != "all":
+                raise ValueError("start_averaging: species must be None, 'all' or a sequence of names, not %r" % (species,))
+            want = names
+        else:
+            want = [str(s) for s in species]
+        if not want:
+            raise ValueError("start_averaging: the species list is empty")
+        idx = []
+        for s in want:
+            if s not in names:
+                raise ValueError("start_averaging: unknown species %r (the mechanism has %s)" % (s, ", ".join(names)))
+            if names.index(s) in idx:
+                raise ValueError("start_averaging: species %r listed twice" % (s,))
+            idx.append(names.index(s))
+        if len(idx) > 16:
+            raise ValueError("start_averaging: %d species, at most 16" % len(idx))
+        return idx
 
     def averages(self) -> dict:
         """The accumulated statistics over the owned columns: ``mean``
@@ -169,11 +219,22 @@ class Simulation:
         averaged time span, or the sample count for ``weight="step"``),
         ``samples`` and ``columns`` = (gi0, gi1).  Solid cells are 0; before
         the first sample everything is 0.  Reading does not disturb the solver
-        state.  ``RuntimeError`` when no accumulator was started."""
+        state.  ``RuntimeError`` when no accumulator was started.
+
+        Only when armed with ``species``: ``species`` (the names, in list
+        order), ``species_mean`` [ns, nxl, ny] and, with second moments,
+        ``species_var`` = MY / W.  Only when armed with ``favre``:
+        ``favre_vars`` = ``("T", "U", "V", "Y:<s>", ...)``, ``favre_mean``
+        [nf, nxl, ny], ``favre_weight`` [nxl, ny] (G) and, with second moments,
+        ``favre_var`` = F / G and ``favre_cov_uv`` = CF / G (0 where G == 0)."""
         a = dict(self.solver.averages())
-        for k in ("mean", "var", "cov_uv"):
+        for k in ("mean", "var", "cov_uv", "species_mean", "species_var", "favre_mean", "favre_var", "favre_cov_uv",
+                  "favre_weight"):
             if k in a:
                 a[k] = np.asarray(a[k])
+        for k in ("species", "favre_vars"):
+            if k in a:
+                a[k] = tuple(str(s) for s in a[k])
         a["time"] = float(a["time"])
         a["samples"] = int(a["samples"])
         a["columns"] = tuple(int(c) for c in a["columns"])

@@ -14,12 +14,20 @@ the two launches and the tick), a step that is no sample adds L, so
 added(1) = L + K and added(10) = L + K / 10.
 
 In the same run a plain device copy that moves the same byte count
-((5 + 2 * planes) * 8 * cells, read + write: a copy of half of it) is timed
+((5 + listed species + 2 * planes) * 8 * cells, read + write: a copy of half of it) is timed
 with the same sync points, and the kernel's bytes / s are set against the
 copy's.
 
+With --favre and / or --species (all | A,B,...; mechanism decks only) the
+entries are instead: off, the base accumulator (second moments) every 1 / 10,
+the same with the options armed (hf2d_stats_accum_x) every 1 / 10, off again,
+so the extended pass stands next to the unarmed run and the base accumulator
+of the same simulation.  Every kernel entry also gives planes * 16 B * cells
+over the kernel's time (plane_GBps: the planes' read + write alone).
+
   python tools/flow_statistics_cost.py --config wedge15|resonator|scramjet
          [--steps 2000] [--warmup 50] [--repeats 3] [--nx N --ny N]
+         [--favre] [--species all|A,B,...]
 """
 from __future__ import annotations
 
@@ -89,6 +97,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--nx", type=int, default=0)
     ap.add_argument("--ny", type=int, default=0)
+    ap.add_argument("--favre", action="store_true", help="also time the accumulator with favre=True")
+    ap.add_argument("--species", default="", help="also time it with these species (all | A,B,...)")
     ap.add_argument("--backend", default="gpu", choices=["gpu", "cpu"], help="cpu: a dry run of the script")
     args = ap.parse_args()
 
@@ -112,27 +122,44 @@ def main():
                    lean_steps=int(getattr(sim.solver, "lns_steps", 0) + getattr(sim.solver, "lnm_steps", 0)), **kw)
         return rec
 
+    species = None
+    if args.species:
+        species = "all" if args.species == "all" else [q for q in args.species.split(",") if q]
+    ns = (len(sim.case.mech_species) if species == "all" else len(species)) if species else 0
+    ext = args.favre or ns > 0
+
+    def plane_count(second, favre, nsp):
+        n = (11 if second else 5) + nsp * (2 if second else 1)
+        if favre:
+            n += 1 + (3 + nsp) * (2 if second else 1) + (1 if second else 0)
+        return n
+
+    # (second moments, favre, species): the base variants, or base and extended side by side
+    variants = [(True, False, None), (True, args.favre, species) if ext else (False, False, None)]
     off = entry("off")
     print(json.dumps(off), flush=True)
     added = {}
-    for second in (True, False):
-        planes = 11 if second else 5
-        nbytes = (5 + 2 * planes) * 8 * nx * ny
+    for second, favre, sp in variants:
+        nsp = ns if sp else 0
+        planes = plane_count(second, favre, nsp)
+        nbytes = (5 + nsp + 2 * planes) * 8 * nx * ny   # the row, the listed partial densities, every plane read + written
+        opts = dict(second_moments=second, favre=bool(favre), species=nsp, planes=planes)
         for every in (1, 10):
-            sim.start_averaging(every=every, second_moments=second)
+            sim.start_averaging(every=every, second_moments=second, favre=bool(favre), species=sp)
             prime(sim, 24)   # (arming dropped the cached graph windows)
-            rec = entry("on", second_moments=second, every=every, bytes_per_sample=nbytes)
+            rec = entry("on", every=every, bytes_per_sample=nbytes, **opts)
             a = sim.averages()
             sim.stop_averaging()
             rec["added_us_per_step"] = round(rec["median"] - off["median"], 3)
             rec["samples"] = a["samples"]
-            rec["finite"] = bool(np.isfinite(a["mean"]).all())
-            added[(second, every)] = rec["added_us_per_step"]
+            rec["finite"] = bool(all(np.isfinite(a[k]).all() for k in a if k.endswith("mean")))
+            added[every] = rec["added_us_per_step"]
             print(json.dumps(rec), flush=True)
-        a1, a10 = added[(second, 1)], added[(second, 10)]
+        a1, a10 = added[1], added[10]
         k_us = (a1 - a10) / 0.9
-        rec = dict(head, entry="kernel", second_moments=second, bytes_per_sample=nbytes, kernel_us=round(k_us, 3),
-                   launch_us=round(a1 - k_us, 3), kernel_GBps=round(nbytes / max(k_us, 1e-9) / 1e3, 1))
+        rec = dict(head, entry="kernel", bytes_per_sample=nbytes, kernel_us=round(k_us, 3),
+                   launch_us=round(a1 - k_us, 3), kernel_GBps=round(nbytes / max(k_us, 1e-9) / 1e3, 1),
+                   plane_GBps=round(planes * 16 * nx * ny / max(k_us, 1e-9) / 1e3, 1), **opts)
         if args.backend == "gpu":
             cp = copy_rate(nbytes, args.repeats)
             rec["copy_us"] = [round(c, 3) for c in cp]
