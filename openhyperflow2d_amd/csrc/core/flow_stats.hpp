@@ -98,6 +98,15 @@ struct StatsExt {
   double* CF = nullptr;   // [N] Favre U, V co-moment (second moments only)
 };
 
+// The base planes of the accumulator on the device (hip/flow_stats.hpp).
+struct FlowStats {
+  double* m = nullptr;   // [STATS_VARS][N] means
+  double* M = nullptr;   // [STATS_VARS][N] weighted squared deviations (second moments only)
+  double* C = nullptr;   // [N] weighted U, V co-moment (second moments only)
+  StatsScalars* sc = nullptr;
+  long c0 = 0, c1 = 0;   // owned cells [c0, c1) of the strip's N (the ghost columns lie outside)
+};
+
 // Planes of N doubles one accumulator holds (base, species, Favre).
 inline size_t stats_plane_count(bool second_moments, bool favre, int ns) {
   size_t n = second_moments ? 2 * STATS_VARS + 1 : STATS_VARS;

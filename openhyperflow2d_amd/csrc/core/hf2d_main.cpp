@@ -32,7 +32,7 @@
 #include "tcpcomm.hpp"
 
 namespace hf2d {
-// Implemented in hip/device_solver.hip when the GPU backend is linked in.
+// Implemented in hip/device_solver.hip (the core unit of the device solver) when the GPU backend is linked in.
 std::unique_ptr<SolverBase> make_gpu_solver(Case& cs, int device) __attribute__((weak));
 std::unique_ptr<SolverBase> make_gpu_strip_solver(Case& cs, int device, int gi0, int gi1, Comm& boot,
                                                   const std::string& transport, std::string& used)

@@ -139,7 +139,7 @@ struct StepParams {
   real wall_blend_f = 0;   // Config::WallBlendFactor
   // device solver, single GPU: the last step of a host call publishes its
   // scalars (dt, error flag, time) into the pinned host mirror itself
-  // (hip/device_solver.hip host_tail; nullptr: hf2d_scalars_out does it)
+  // (hip/lean_tile.hpp host_mirror_tail, DeviceSolver::host_tail; nullptr: hf2d_scalars_out does it)
   void* host_sc = nullptr;
   unsigned* host_done = nullptr;
   // device lean tile kernel, single GPU (speed only, the value is the same):

@@ -343,6 +343,12 @@ class DeviceSolver : public SolverBase {
   StepDone step_lean_ns(const StepCtx& c);   // (with its entry step)
   StepDone lnm_step(const StepCtx& c);       // (likewise)
   StepDone step_split(const StepCtx& c, bool to_lns);
+  void wall_heat(const StepCtx& c);          // wall heat transfer after the step (non-adiabatic walls)
+  // mailbox transport, multi-workgroup kernels: a list's edge columns into the
+  // neighbours' mailboxes, the publishing tail alone, mailbox -> ghost columns
+  void p2p_push(const struct ColList& L, void* on_stream, int dt_slot, int fold_dt, int finish);
+  void p2p_finish(int dt_slot);
+  void p2p_unpack(const struct ColList& L, void* on_stream);
   // edge-first steps of the host transports: the comm stream and its events;
   // the edge part's halo (after ev_edge) on that stream, the dt MIN after it
   void overlap_streams();

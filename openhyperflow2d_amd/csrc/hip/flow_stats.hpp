@@ -26,14 +26,6 @@ namespace hf2d {
 constexpr int STATS_BLOCK = 256;
 static_assert(STATS_VARS == PROBE_VARS, "the accumulated row is the probe recorder's");
 
-struct FlowStats {
-  double* m = nullptr;   // [STATS_VARS][N] means
-  double* M = nullptr;   // [STATS_VARS][N] weighted squared deviations (second moments only)
-  double* C = nullptr;   // [N] weighted U, V co-moment (second moments only)
-  StatsScalars* sc = nullptr;
-  long c0 = 0, c1 = 0;   // owned cells [c0, c1) of the strip's N (the ghost columns lie outside)
-};
-
 #ifdef __HIPCC__
 __global__ __launch_bounds__(64) void hf2d_stats_tick(StatsScalars* s, const DevScalars* sc) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;

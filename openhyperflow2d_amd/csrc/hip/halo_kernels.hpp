@@ -4,10 +4,10 @@
 //   hf2d_p2p_xchg          xGMI mailbox exchange in one workgroup (P2PArgs)
 //   hf2d_p2p_complete      ghost columns + dt after fused tile steps
 //   hf2d_p2p_push/finish/unpack   multi-workgroup mailbox exchange
-// Part of the device_solver.hip translation unit.
+// Included by transport.hip only (the kernels here are not templates).
 #pragma once
 
-#include "lean_tile.hpp"
+#include "dev_common.hpp"
 
 namespace hf2d {
 

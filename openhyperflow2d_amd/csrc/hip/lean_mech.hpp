@@ -40,52 +40,6 @@
 
 namespace hf2d {
 
-constexpr int LNM_NSB = 9;   // species block of the kernel (mechanisms up to 9 species)
-constexpr int LNM_TILE = 16;  // tile edge (256 cells, one per thread; the ring is exactly one wavefront)
-
-struct LnmArrays {
-  long N = 0;
-  const MechData* mech = nullptr;
-  int nsp = 0, bath = 0;
-  const real* Sp = nullptr;   // Sp^m (flow + turbulence equations, [k * N + idx])
-  real* Sp_out = nullptr;     // Sp^{m+1}
-  const real* Ys = nullptr;   // species of S^m (after the kinetics), [s * N + idx]
-  real* Ys_out = nullptr;     // species of Sp^{m+1} (the kinetics then update them in place)
-  real* beta = nullptr;       // in place
-  real* betas = nullptr;
-  const real *Ui = nullptr, *Vi = nullptr, *Ti = nullptr;   // level m-1 (gradients, velocity recovery)
-  real *Uo = nullptr, *Vo = nullptr, *To = nullptr;         // level m
-  const real *mui = nullptr, *lami = nullptr, *mu_ti = nullptr;
-  real *muo = nullptr, *lamo = nullptr, *mu_to = nullptr;
-  const real *Tsi = nullptr, *psi = nullptr, *CPsi = nullptr, *ksi = nullptr;   // state of level m
-  real *Tso = nullptr, *pso = nullptr, *CPso = nullptr, *kso = nullptr;         // state of level m+1
-  const real *l_min = nullptr, *y_plus = nullptr, *BGX = nullptr, *BGY = nullptr, *grad = nullptr;
-  real* Src = nullptr;      // turbulence sources, in place
-  real* SrcAdd = nullptr;   // wall sources, in place
-  const real *gA = nullptr, *gB = nullptr, *gF = nullptr;   // turbulence fluxes of nodes without the model
-  const real* dSdx_in = nullptr;
-  const real* dSdy_in = nullptr;
-  real* dSdx_out = nullptr;
-  real* dSdy_out = nullptr;
-  const real* dSdxs_in = nullptr;   // species Cauchy dS (nullptr: no node needs them)
-  const real* dSdys_in = nullptr;
-  real* dSdxs_out = nullptr;
-  real* dSdys_out = nullptr;
-  const u64* CT = nullptr;
-  const u64* TT = nullptr;
-  const uint8_t* nb = nullptr;
-  const uint8_t* gf = nullptr;
-  int* hot = nullptr;   // reacting cells of the step (kinetics list)
-  unsigned* hot_n = nullptr;   // ... and their count (DevScalars::hot_cnt / hot_cnt2 of the slot)
-  int part = 0;   // tiles of this launch: 0 all, 1 the strip's edge tile columns, 2 the others (comm overlap)
-  unsigned long long* tr = nullptr;   // phase trace (HF2D_LNM_TRACE): 12 clocks per workgroup
-  // xGMI mailboxes: the previous step's HALO_LNS list (lg) and the exchange
-  // arguments (xg, device copies): the edge tiles copy that step's halo from
-  // the mailbox into the ghost columns first (fx_ghost_prologue)
-  const struct FusedX* xg = nullptr;
-  const struct ColList* lg = nullptr;
-};
-
 // Tile of the lean mechanism step: TI columns x LNM_TILE rows, one cell per
 // thread.  TI = 16: the 64 ring cells take a second fill on wavefront 0;
 // TI = 12: 192 own + 56 ring cells, every thread one fill.

@@ -27,37 +27,9 @@
 #pragma once
 
 #include "../core/lean_euler.hpp"
+#include "solver_args.hpp"
 
 namespace hf2d {
-
-// Kernel argument block.  Level m-1 = the primitives the fill F_m reads
-// (prim_old of the split fill), level m = the ones it produces.
-struct LnsArrays {
-  long N = 0;
-  const real* Sp = nullptr;   // Sp^m [k * N + idx] (live equations)
-  real* Sp_out = nullptr;     // Sp^{m+1}
-  real* beta = nullptr;       // in place
-  const real *Ui = nullptr, *Vi = nullptr, *Ti = nullptr;
-  real *Uo = nullptr, *Vo = nullptr, *To = nullptr;
-  const real *CPi = nullptr, *mui = nullptr, *lami = nullptr, *kki = nullptr, *mu_ti = nullptr;
-  real *CPo = nullptr, *muo = nullptr, *lamo = nullptr, *kko = nullptr, *mu_to = nullptr;
-  const real *R = nullptr, *BGX = nullptr, *BGY = nullptr, *grad = nullptr, *l_min = nullptr, *y_plus = nullptr;
-  // in place (a ring evaluation of another tile discards these outputs, so
-  // only the owner's read-before-write matters)
-  real* SrcAdd = nullptr;
-  real* Src = nullptr;
-  // generic fluxes: the turbulence equations' of a node without a k-eps
-  // model bit are never rewritten by the fill (constant while lean)
-  const real *gA = nullptr, *gB = nullptr, *gF = nullptr;
-  const real* dSdx_in = nullptr;
-  const real* dSdy_in = nullptr;
-  real* dSdx_out = nullptr;
-  real* dSdy_out = nullptr;
-  const u64* CT = nullptr;
-  const u64* TT = nullptr;
-  const uint8_t* nb = nullptr;
-  const uint8_t* gf = nullptr;
-};
 
 // live equations: SGL 0..3; SGT 0..3 + k, eps (LDS plane q(k))
 template <int MODE>

@@ -1,0 +1,362 @@
+// Observers of the run: monitor points, the per-step probe recorder
+// (probe_history.hpp) and the time-averaged flow statistics (flow_stats.hpp).
+
+#include "device_impl.hpp"
+#include "flow_stats.hpp"
+
+namespace hf2d {
+
+// K8 monitors: p and Tg of the probe cells this rank owns (idx < 0: not
+// owned) gathered on the device, so an output step moves 16 bytes per probe
+// instead of the whole state.
+__global__ void hf2d_probe_gather(const long* idx, int n, const real* p, const real* T, real* out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const long c = idx[t];
+  out[2 * t] = c >= 0 ? p[c] : 0.0;
+  out[2 * t + 1] = c >= 0 ? T[c] : 0.0;
+}
+
+void DeviceSolver::sample_monitors(std::vector<MonitorPoint>& mp) {
+  if (mp.empty()) return;
+  flush_pending();
+  p2p_complete();
+  Impl& m = *impl;
+  if (lns_state) lns_materialize();
+  const int n = (int)mp.size();
+  std::vector<long> idx(n, -1);
+  for (int q = 0; q < n; q++) {
+    const int i = (int)(mp[q].x / cs.cfg.dx), j = (int)(mp[q].y / cs.cfg.dy);
+    if (cs.J.in(i, j) && i >= gi0 && i < gi1) idx[q] = (long)(i - gi0 + l_off) * h.ny + j;
+  }
+  if ((int)probe_idx_host.size() != n) {
+    probe_idx_host.assign(n, -2);
+    probe_buf_host.assign(2 * n, 0.0);
+    impl->probe_idx = m.mem.alloc<long>(n);
+    impl->probe_out = m.mem.alloc<real>(2 * n);
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+  if (idx != probe_idx_host) {
+    probe_idx_host = idx;
+    HIP_CHECK(hipMemcpyAsync(m.probe_idx, probe_idx_host.data(), n * sizeof(long), hipMemcpyHostToDevice, m.stream));
+  }
+  // current pressure: the lean arrays while they are authoritative
+  const real* p = lean_state ? m.P2[pbuf] : m.p;
+  hipLaunchKernelGGL(hf2d_probe_gather, dim3((n + 63) / 64), dim3(64), 0, m.stream, m.probe_idx, n, p, m.Tg[pbuf],
+                     m.probe_out);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(probe_buf_host.data(), m.probe_out, 2 * n * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  for (int q = 0; q < n; q++) {
+    real pv = probe_buf_host[2 * q], Tv = probe_buf_host[2 * q + 1];
+    const int i = (int)(mp[q].x / cs.cfg.dx), j = (int)(mp[q].y / cs.cfg.dy);
+    if (comm->size() > 1) {   // exactly one rank owns the probe
+      pv = comm->allreduce_sum(pv);
+      Tv = comm->allreduce_sum(Tv);
+    } else if (!cs.J.in(i, j)) {
+      continue;
+    }
+    mp[q].p = pv;
+    mp[q].T = Tv;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Per-step probe recorder (hip/probe_history.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::record_probes(const std::vector<std::pair<int, int>>& cells, long capacity) {
+  check_probe_cells(cells, capacity);
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const int n = (int)cells.size();
+  probe_rec_idx.assign(n, -1);
+  for (int q = 0; q < n; q++) {
+    const int i = cells[q].first, j = cells[q].second;
+    if (i < gi0 || i >= gi1) continue;   // another strip's column
+    const long c = (long)(i - gi0 + l_off) * h.ny + j;
+    // (a trimmed strip rank's Case could not check its flags in check_probe_cells)
+    if (has_all(h.CT[c], CT_SOLID) || !has_all(h.CT[c], CT_NODE_IS_SET))
+      throw std::invalid_argument("record_probes: cell (" + std::to_string(i) + ", " + std::to_string(j) +
+                                  ") is solid or not set");
+    probe_rec_idx[q] = c;
+  }
+  // (outside any capture: flush_pending ran the queued steps, and a capture
+  // only lives inside run_graph)
+  ProbeRing r;
+  r.n = n;
+  r.cap = (int)std::min<long>(capacity, 0x7fffffffL);
+  long* idx = m.mem.alloc<long>(n);
+  r.idx = idx;
+  r.rows = m.mem.alloc<real>((size_t)r.cap * n * PROBE_VARS);
+  r.times = m.mem.alloc<double>((size_t)r.cap);
+  r.count = m.mem.alloc<unsigned long long>(1);
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  HIP_CHECK(hipMemcpyAsync(idx, probe_rec_idx.data(), n * sizeof(long), hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.ring = r;
+  probe_cap = r.cap;
+  probe_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+void DeviceSolver::clear_probe_history() {
+  if (!probe_cap) return;
+  flush_pending();
+  Impl& m = *impl;
+  HIP_CHECK(hipMemsetAsync(m.ring.count, 0, sizeof(unsigned long long), m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+ProbeHistory DeviceSolver::probe_history() {
+  if (!probe_cap) throw std::runtime_error("probe_history: no recorder armed (record_probes)");
+  flush_pending();
+  Impl& m = *impl;
+  const ProbeRing& r = m.ring;
+  const size_t row = (size_t)r.n * PROBE_VARS;
+  unsigned long long total = 0;
+  std::vector<real> rows((size_t)r.cap * row);
+  std::vector<double> tp((size_t)r.cap);
+  HIP_CHECK(hipMemcpyAsync(&total, r.count, sizeof total, hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipMemcpyAsync(rows.data(), r.rows, rows.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipMemcpyAsync(tp.data(), r.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  ProbeHistory H;
+  H.nprobes = r.n;
+  H.total = (long)total;
+  const long cap = r.cap, n = std::min<long>(H.total, cap), first = H.total > cap ? H.total % cap : 0;
+  H.times.resize(n);
+  H.values.resize((size_t)n * row);
+  for (long k = 0; k < n; k++) {
+    const long s = (first + k) % cap;
+    // the device accumulates time since the start; the host's time is
+    // global_time + (time_part - time_offset) (sync_scalars, summary)
+    const real part = tp[s] - time_offset;
+    H.times[k] = cs.global_time + part;
+    std::copy(rows.begin() + s * row, rows.begin() + (s + 1) * row, H.values.begin() + k * row);
+  }
+  H.owned.resize(r.n);
+  for (int q = 0; q < r.n; q++) H.owned[q] = probe_rec_idx[q] >= 0 ? 1 : 0;
+  return H;
+}
+
+// Last launch of a step: the row of every probe from the post-step buffers,
+// in the representation that is authoritative now (the views download() /
+// lns_materialize() would read).
+int DeviceSolver::post_step_view(SoA& s) const {
+  const Impl& m = *impl;
+  int kind = PR_GATHER;
+  if (lns_state) {
+    // lean N-S / mechanism: Sp^{m+1} and the lagged level (lns_materialize's input view)
+    s = m.view(h, 1 - sbuf, abuf, dsbuf, 1 - pbuf);
+    const Impl::Levels x = m.levels();
+    if (m.mech) {
+      kind = PR_MECH;
+      s.kk = x.kk[cbuf];         // the lagged k of fill_node's skip test
+      s.Tg = m.Tst[1 - cbuf];    // stored state of the new level
+      s.p = x.p[1 - cbuf];
+      // the post-kinetics species of Sp^{m+1} (lnm_arrays: Ys[sb] beside
+      // S[1 - sb]), which lns_materialize leaves where they are and download()
+      // reads; the other paths' view holds Ys[sbuf] already
+      s.Ys = m.Ys[sbuf];
+    } else {
+      kind = sk_mode == SK_SGT ? PR_SGT : PR_SGL;
+      s.CP = x.CP[1 - cbuf];
+      s.mu = x.mu[1 - cbuf];
+      s.lam = x.lam[1 - cbuf];
+      s.kk = x.kk[1 - cbuf];
+      s.mu_t = x.mu_t[1 - cbuf];
+    }
+  } else {
+    s = m.view(h, sbuf, abuf, dsbuf, pbuf);
+    if (lean_state) {
+      s.p = m.P2[pbuf];
+      if (!lean_T_stored) kind = PR_LEAN;
+    }
+  }
+  return kind;
+}
+
+void DeviceSolver::launch_probe_record(const StepParams& P) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
+  const dim3 g(1), b(PROBE_MAX);
+  switch (kind) {
+    case PR_SGL: hipLaunchKernelGGL(hf2d_probe_record<PR_SGL>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    case PR_SGT: hipLaunchKernelGGL(hf2d_probe_record<PR_SGT>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    case PR_MECH: hipLaunchKernelGGL(hf2d_probe_record<PR_MECH>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    case PR_LEAN: hipLaunchKernelGGL(hf2d_probe_record<PR_LEAN>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+    default: hipLaunchKernelGGL(hf2d_probe_record<PR_GATHER>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Whole-field time averages (hip/flow_stats.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::start_averaging(int every, bool second_moments, bool step_weight, bool favre,
+                                   const std::vector<int>& species) {
+  check_averaging(every, species, h.nsp);
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const size_t N = (size_t)h.N, planes = stats_plane_count(second_moments, favre, (int)species.size());
+  FlowStats f = m.stats;
+  if (planes > m.stats_planes) {   // (arming again with as many planes or fewer reuses them)
+    f.m = m.mem.alloc<double>(planes * N);
+    m.stats_planes = planes;
+  }
+  if (!f.sc) f.sc = m.mem.alloc<StatsScalars>(1);
+  f.M = second_moments ? f.m + STATS_VARS * N : nullptr;
+  f.C = second_moments ? f.m + 2 * STATS_VARS * N : nullptr;
+  f.c0 = (long)l_off * h.ny;
+  f.c1 = f.c0 + (long)(gi1 - gi0) * h.ny;
+  StatsExt x{};
+  x.ns = (int)species.size();
+  std::copy(species.begin(), species.end(), x.sp);
+  stats_ext_planes(x, f.m, N, second_moments, favre);
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  StatsScalars s0{};
+  s0.every = every;
+  s0.step_weight = step_weight ? 1 : 0;
+  s0.t_off = time_offset;
+  HIP_CHECK(hipMemcpyAsync(f.sc, &s0, sizeof s0, hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipMemsetAsync(f.m, 0, planes * N * sizeof(double), m.stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, f.sc, m.sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.stats = f;
+  m.stats_x = x;
+  m.stats_used = planes;
+  stats_second = second_moments;
+  stats_favre = favre;
+  stats_species = species;
+  stats_on = stats_armed = true;
+  stats_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+void DeviceSolver::reset_averaging() {
+  if (!stats_on) return;
+  flush_pending();
+  Impl& m = *impl;
+  HIP_CHECK(hipMemsetAsync(m.stats.m, 0, m.stats_used * (size_t)h.N * sizeof(double), m.stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, m.stats.sc, m.sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+void DeviceSolver::stop_averaging() {
+  if (!stats_on) return;
+  flush_pending();
+  stats_on = false;
+  stats_gen++;   // the cached windows hold the accumulate nodes
+}
+
+FlowAverages DeviceSolver::averages() {
+  if (!stats_armed) throw std::runtime_error("averages: no accumulator armed (start_averaging)");
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const FlowStats& f = m.stats;
+  const StatsExt& x = m.stats_x;
+  FlowAverages A;
+  A.gi0 = gi0;
+  A.gi1 = gi1;
+  A.ny = h.ny;
+  A.second_moments = stats_second;
+  A.favre = stats_favre;
+  A.species = stats_species;
+  const size_t n = (size_t)(f.c1 - f.c0), N = (size_t)h.N;
+  StatsScalars sc;
+  HIP_CHECK(hipMemcpyAsync(&sc, f.sc, sizeof sc, hipMemcpyDeviceToHost, m.stream));
+  auto planes = [&](const double* src, int np, std::vector<double>& dst) {
+    dst.resize((size_t)np * n);
+    for (int k = 0; k < np; k++)
+      HIP_CHECK(hipMemcpyAsync(dst.data() + k * n, src + k * N + f.c0, n * sizeof(double), hipMemcpyDeviceToHost,
+                               m.stream));
+  };
+  const int ns = x.ns, nf = STATS_FAVRE_BASE + ns;
+  planes(f.m, STATS_VARS, A.mean);
+  planes(x.mY, ns, A.species_mean);
+  if (stats_favre) {
+    planes(x.G, 1, A.favre_weight);
+    planes(x.f, nf, A.favre_mean);
+  }
+  if (stats_second) {
+    planes(f.M, STATS_VARS, A.var);
+    planes(f.C, 1, A.cov_uv);
+    planes(x.MY, ns, A.species_var);
+    if (stats_favre) {
+      planes(x.F, nf, A.favre_var);
+      planes(x.CF, 1, A.favre_cov_uv);
+    }
+  }
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  A.time = sc.W;
+  A.samples = (long)sc.samples;
+  if (stats_second) A.finish(sc.W);
+  return A;
+}
+
+// After the recorder's launch: the tick decides on the device whether the
+// step is a sample and forms its weight; the cell pass reads the same view
+// the recorder reads.  Nothing here allocates, copies or synchronises.
+template <int KIND>
+static void launch_stats_kind(hipStream_t st, unsigned nblk, bool second, const StepParams& P, const SoA& s,
+                              const FlowStats& f) {
+  if (second)
+    hipLaunchKernelGGL((hf2d_stats_accum<KIND, true>), dim3(nblk), dim3(STATS_BLOCK), 0, st, P, s, f);
+  else
+    hipLaunchKernelGGL((hf2d_stats_accum<KIND, false>), dim3(nblk), dim3(STATS_BLOCK), 0, st, P, s, f);
+}
+
+// the same pass with Favre averages or species statistics armed
+template <int KIND>
+static void launch_stats_x_kind(hipStream_t st, unsigned nblk, bool second, bool favre, const StepParams& P,
+                                const SoA& s, const FlowStats& f, const StatsExt& x) {
+  const dim3 g(nblk), b(STATS_BLOCK);
+  if (second && favre)
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, true, true>), g, b, 0, st, P, s, f, x);
+  else if (second)
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, true, false>), g, b, 0, st, P, s, f, x);
+  else if (favre)
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, false, true>), g, b, 0, st, P, s, f, x);
+  else
+    hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, false, false>), g, b, 0, st, P, s, f, x);
+}
+
+void DeviceSolver::launch_stats(const StepParams& P) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
+  const FlowStats& f = m.stats;
+  hipLaunchKernelGGL(hf2d_stats_tick, dim3(1), dim3(64), 0, m.stream, f.sc, m.sc);
+  HIP_CHECK(hipGetLastError());
+  const unsigned nblk = (unsigned)((f.c1 - f.c0 + STATS_BLOCK - 1) / STATS_BLOCK);
+  if (stats_favre || m.stats_x.ns > 0) {
+    const StatsExt& x = m.stats_x;
+    // (a listed species is a plane of the view's block: check_averaging)
+    if (x.ns > 0 && (!s.Ys || s.nsp != h.nsp)) throw std::runtime_error("flow statistics: the step's view holds no species block");
+    switch (kind) {
+      case PR_SGL: launch_stats_x_kind<PR_SGL>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      case PR_SGT: launch_stats_x_kind<PR_SGT>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      case PR_MECH: launch_stats_x_kind<PR_MECH>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      case PR_LEAN: launch_stats_x_kind<PR_LEAN>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+      default: launch_stats_x_kind<PR_GATHER>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  switch (kind) {
+    case PR_SGL: launch_stats_kind<PR_SGL>(m.stream, nblk, stats_second, P, s, f); break;
+    case PR_SGT: launch_stats_kind<PR_SGT>(m.stream, nblk, stats_second, P, s, f); break;
+    case PR_MECH: launch_stats_kind<PR_MECH>(m.stream, nblk, stats_second, P, s, f); break;
+    case PR_LEAN: launch_stats_kind<PR_LEAN>(m.stream, nblk, stats_second, P, s, f); break;
+    default: launch_stats_kind<PR_GATHER>(m.stream, nblk, stats_second, P, s, f); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace hf2d

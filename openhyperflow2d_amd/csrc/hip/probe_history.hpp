@@ -28,18 +28,6 @@
 
 namespace hf2d {
 
-constexpr int PROBE_MAX = 64;    // one lane per probe
-constexpr int PROBE_VARS = 5;    // p, T, rho, U, V
-enum { PR_GATHER = 0, PR_SGL = 1, PR_SGT = 2, PR_MECH = 3, PR_LEAN = 4 };
-
-struct ProbeRing {
-  const long* idx = nullptr;   // local cell of each probe (< 0: another strip's column)
-  int n = 0, cap = 0;
-  real* rows = nullptr;        // [cap][n][PROBE_VARS]
-  double* times = nullptr;     // [cap] DevScalars::time_part after the step
-  unsigned long long* count = nullptr;   // rows written since arming
-};
-
 // fill_compute() accessor of one node without neighbours over the SoA view
 // the materialise fill reads (DeviceSolver::lns_materialize): every neighbour
 // resolves to the node itself, so the fluxes, gradients and turbulence

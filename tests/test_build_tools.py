@@ -19,6 +19,33 @@ def test_cmake_configures(tmp_path):
     for tgt in ("_hf2d", "hf2d_cpu", "hf2d"):
         assert f"build {tgt}" in ninja
     assert "--offload-arch=gfx950" in ninja
+    # every translation unit of csrc/hip is built (bind/module.cpp calls into each)
+    hip = os.path.join(ROOT, "openhyperflow2d_amd", "csrc", "hip")
+    units = sorted(f for f in os.listdir(hip) if f.endswith(".hip"))
+    assert units
+    for u in units:
+        assert os.path.join("csrc", "hip", u) in ninja, u
+
+
+LLVM_TOOLS = [os.path.join("/opt/rocm/lib/llvm/bin", t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
+
+
+@pytest.mark.skipif(not all(os.path.exists(t) for t in LLVM_TOOLS), reason="LLVM binary tools missing")
+def test_every_kernel_is_compiled_in_one_code_object(native):
+    """The solver is split by kernel family: the extension holds several gfx950 code
+    objects and no kernel name occurs in two (metadata notes only, no GPU)."""
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import kernel_resources as kr
+    finally:
+        sys.path.pop(0)
+    objs = kr.resources_by_object(native.__file__)
+    assert len(objs) > 1
+    assert all(objs), "a code object without kernels in its notes"
+    assert kr.duplicates(objs) == []
+    assert len(kr.resources(native.__file__)) == sum(len(o) for o in objs)
 
 
 def test_plot_helpers_write_gnuplot_scripts(native, tmp_path):

@@ -41,8 +41,9 @@ def code_objects(so, tmp):
     return out
 
 
-def resources(so):
-    res = {}
+def resources_by_object(so):
+    """One {kernel name: resources} per gfx950 code object that holds kernels (one per .hip)."""
+    objs = []
     with tempfile.TemporaryDirectory() as tmp:
         for co in code_objects(so, tmp):
             notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True,
@@ -52,9 +53,25 @@ def resources(so):
                 continue
             txt = notes[notes.rfind("---", 0, i):]
             txt = txt[:txt.find("\n...")]
-            for k in yaml.safe_load(txt)["amdhsa.kernels"]:
-                res[k[".name"]] = tuple(k.get(x, 0) for x in KEYS)
-    return res
+            objs.append({k[".name"]: tuple(k.get(x, 0) for x in KEYS) for k in yaml.safe_load(txt)["amdhsa.kernels"]})
+    return objs
+
+
+def duplicates(objs):
+    """Kernel names that occur in more than one code object (a kernel compiled twice)."""
+    seen, dup = set(), set()
+    for o in objs:
+        dup |= seen & set(o)
+        seen |= set(o)
+    return sorted(dup)
+
+
+def resources(so):
+    objs = resources_by_object(so)
+    dup = duplicates(objs)
+    if dup:
+        raise RuntimeError("%s: kernels in more than one code object: %s" % (so, ", ".join(demangle(dup))))
+    return {n: r for o in objs for n, r in o.items()}
 
 
 def demangle(names):
@@ -68,8 +85,12 @@ def main():
     ap.add_argument("--other", default=None)
     ap.add_argument("--match", nargs="*", default=[])
     a = ap.parse_args()
-    h = resources(a.so)
-    o = resources(a.other) if a.other else None
+    try:
+        h = resources(a.so)
+        o = resources(a.other) if a.other else None
+    except RuntimeError as e:
+        print("error: %s" % e, file=sys.stderr)
+        return 1
     names = sorted(h)
     pretty = dict(zip(names, demangle(names)))
     print("%-70s %5s %4s %4s %5s %5s %6s %6s" % ("kernel", "vgpr", "agpr", "sgpr", "vspil", "sspil", "scratch", "lds"))
