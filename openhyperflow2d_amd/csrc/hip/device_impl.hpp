@@ -125,7 +125,6 @@ struct DeviceSolver::Impl {
   StatsExt stats_x{};          // species list and the favre / species planes inside them
   DevScalars* sc = nullptr;
   DevScalars* sc_host = nullptr;   // pinned
-  bool sc_kernel = true;           // sync_scalars: hf2d_scalars_out instead of a copy (HF2D_SC_KERNEL=0: copy)
   // single GPU: the last (output) lean tile step of a host call wrote the
   // scalars into sc_host itself (DeviceSolver::host_tail); sync_scalars then
   // only waits

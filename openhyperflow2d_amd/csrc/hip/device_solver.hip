@@ -94,9 +94,7 @@ DeviceSolver::DeviceSolver(Case& c, int device, int gi0_, int gi1_) : SolverBase
   if (const char* e = std::getenv("HF2D_CHEM_KERNEL")) chem_kernel = std::atoi(e);   // 1 compiled 2 MFMA 3 generic 4 hiprtc
   if (const char* e = std::getenv("HF2D_GRAD_EVERY")) grad_every = std::string(e) != "0";
   if (const char* e = std::getenv("HF2D_LNM_TI")) lnm_ti = std::atoi(e);
-  if (const char* e = std::getenv("HF2D_PUSH_PER")) push_per = std::atoi(e);
   if (const char* e = std::getenv("HF2D_STAGGER")) tile_stagger = std::atoi(e);
-  if (const char* e = std::getenv("HF2D_SC_KERNEL")) impl->sc_kernel = std::string(e) != "0";
   if (const char* e = std::getenv("HF2D_HOST_TAIL")) host_tail = std::string(e) != "0";
   if (const char* e = std::getenv("HF2D_DT_READ")) dt_read_mode = std::atoi(e);
   if (const char* e = std::getenv("HF2D_SKIP_SAME")) tile_skip_same = std::string(e) != "0";
@@ -535,12 +533,10 @@ void DeviceSolver::sync_scalars() {
     // shards, dt_bits, dt_lag, time_part and neg_T of sc_host; the other
     // DevScalars fields there (iter, scenario beta / CFL, dt_val, hot counts)
     // are stale, so this function must read nothing else below this point
-    // (hf2d_scalars_out / the memcpy refresh the whole header).
-  } else if (m.sc_kernel) {
+    // (hf2d_scalars_out refreshes the whole header).
+  } else {
     hipLaunchKernelGGL(hf2d_scalars_out, dim3(1), dim3(WAVE), 0, m.stream, m.sc, m.sc_host, (int)(nstep % 3));
     HIP_CHECK(hipGetLastError());
-  } else {
-    HIP_CHECK(hipMemcpyAsync(m.sc_host, m.sc, sizeof(DevScalars), hipMemcpyDeviceToHost, m.stream));
   }
   HIP_CHECK(hipStreamSynchronize(m.stream));
   const int slot = nstep % 3;
@@ -614,8 +610,8 @@ uint64_t DeviceSolver::mode_signature() const {
                         lean_tj, lean_nt, lean_wgcu, (int)(p2p_fuse && impl->p2p.on), (int)(sgl && sgl_ok), lns_state,
                         (int)lean_ns, (int)lean_mech, sbuf, abuf, dsbuf, pbuf, cbuf,
                         // (settings a captured launch bakes in: the cpt gate and the stagger rounds,
-                        // the mailbox push kernel, the dt read, the skipped stores, the ghost prologue)
-                        cu_count, push_per, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue,
+                        // the dt read, the skipped stores, the ghost prologue)
+                        cu_count, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue,
                         // (a window captured before record_probes has no recorder launch, one
                         // captured before arming again writes the previous ring)
                         probe_gen,

@@ -218,8 +218,6 @@ class DeviceSolver : public SolverBase {
   bool lean_sg = true;     // single-gas specialisation (lean_euler.hpp) if eligible
   int lean_tj = 0;         // tile height override (0: auto, ny split in <= 64)
   int lean_wgcu = 0;       // >0: at most this many tile workgroups resident per CU (LDS request)
-  int push_per = 1;        // halo values per thread of the mailbox push kernel (1, 4, 16)
-  int lean_occ = 0;        // occupancy target (waves/SIMD) for the hot kernel: 0 or 6 (cpt 1)
   int lean_cpt = 2;        // cells per thread in the tiled kernel: 1 or 2 (2: measured ~20% faster)
   int lean_nt = 256;       // threads per tile workgroup: 256, or 128 / 64 (single gas; small strips)
   int cu_count = 256;

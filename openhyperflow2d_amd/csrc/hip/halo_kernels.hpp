@@ -252,64 +252,36 @@ __global__ __launch_bounds__(P2P_THREADS) void hf2d_p2p_complete(ColList Lc, int
 }
 
 // Multi-workgroup mailbox exchange, push half (the mechanism step and every
-// other p2p exchange with p2p_fuse): each thread loads up to PER boundary
-// values of the fields in Lc (column first + o / last - o) and stores them
-// into the neighbours' mailboxes; the last workgroup publishes and, fold,
-// folds the peers' dt into dslot (fx_tail); hf2d_p2p_unpack follows.
+// other p2p exchange with p2p_fuse): each thread loads one boundary value of
+// the fields in Lc (column first + o / last - o) and stores it into the
+// neighbour's mailbox; the last workgroup publishes and, fold, folds the
+// peers' dt into dslot (fx_tail); hf2d_p2p_unpack follows.
 // publish = 0: the pushes only (drained); a later hf2d_p2p_finish publishes
 // the step -- the mechanism step pushes its edge tiles' halo before its
 // interior tiles run.
-template <int PER>
+// One value per thread (135 workgroups on the scramjet's 8-rank strip) pushed
+// the 43-field mechanism halo in 7.0 us against 15.4 us with 16 values per
+// thread on 9 workgroups (profiles/rejected_variants.md).
 __global__ __launch_bounds__(BLOCK) void hf2d_p2p_push(ColList Lc, int first, int last, int ny, int cnt, FusedX X,
                                                       DevScalars* sc, int dslot, int fold, int publish) {
   const unsigned long long seq_prev = *X.seq;
   const int pn = (int)((seq_prev + 1) & 1);
-  // value u of a thread: base + u * BLOCK (consecutive lanes, consecutive
-  // addresses: with PER consecutive values per thread every load and mailbox
-  // store instruction touched 64 different lines)
-  const long base = (long)blockIdx.x * BLOCK * PER + threadIdx.x;
-  real v[PER];
-#pragma unroll
-  for (int u = 0; u < PER; u++) {
-    const long t = base + (long)u * BLOCK;
-    if (t < 2L * cnt) {
-      const int side = t < cnt ? 0 : 1;
-      const int tt = (int)(t - (long)side * cnt), f = tt / ny, j = tt - f * ny;
-      if ((X.sides & (1 << side)) && !(X.skip & 8))
-        v[u] = Lc.f[f][(long)(side == 0 ? first + Lc.o[f] : last - Lc.o[f]) * ny + j];
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < PER; u++) {
-    const long t = base + (long)u * BLOCK;
-    if (t < 2L * cnt) {
-      const int side = t < cnt ? 0 : 1;
-      const int tt = (int)(t - (long)side * cnt);
-      // the left neighbour receives "from right", the right one "from left"
-      if ((X.sides & (1 << side)) && !(X.skip & 2))
-        p2p_store((side == 0 ? X.peer_recv_l + ((long)pn * 2 + 1) * X.cap : X.peer_recv_r + ((long)pn * 2) * X.cap) +
-                      tt,
-                  v[u]);
-    }
+  const long t = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (t < 2L * cnt) {
+    const int side = t < cnt ? 0 : 1;
+    const int tt = (int)(t - (long)side * cnt), f = tt / ny, j = tt - f * ny;
+    real v;
+    if ((X.sides & (1 << side)) && !(X.skip & 8))
+      v = Lc.f[f][(long)(side == 0 ? first + Lc.o[f] : last - Lc.o[f]) * ny + j];
+    // the left neighbour receives "from right", the right one "from left"
+    if ((X.sides & (1 << side)) && !(X.skip & 2))
+      p2p_store((side == 0 ? X.peer_recv_l + ((long)pn * 2 + 1) * X.cap : X.peer_recv_r + ((long)pn * 2) * X.cap) + tt,
+                v);
   }
   vm_drain();
   if (!publish) return;
   __syncthreads();
   if (threadIdx.x < WAVE && !(X.skip & 1)) fx_tail(X, sc, dslot, seq_prev, fold != 0);
-}
-
-using PushK = void (*)(ColList, int, int, int, int, FusedX, DevScalars*, int, int, int);
-// values per thread of the push kernel (HF2D_PUSH_PER: 1, 4 or 16) and its
-// grid: one value per thread (135 workgroups on the scramjet's 8-rank strip)
-// pushed the 43-field mechanism halo in 7.0 us against 15.4 us with 16 values
-// per thread on 9 workgroups (rocprofv3 kernel trace of tools/exchange_loopback.py;
-// loopback exchange 18.7 -> 8.2 us)
-inline PushK push_kernel(int per) {
-  return per == 16 ? hf2d_p2p_push<16> : per == 4 ? hf2d_p2p_push<4> : hf2d_p2p_push<1>;
-}
-inline unsigned push_grid(int per, int cnt) {
-  const int p = per == 16 || per == 4 ? per : 1;
-  return (unsigned)std::max(1, (2 * cnt + BLOCK * p - 1) / (BLOCK * p));
 }
 
 // One workgroup: publish the step whose halo an earlier hf2d_p2p_push

@@ -1,7 +1,7 @@
 // Inviscid lean tile kernels (lean_euler.hpp on LDS tiles):
 //   lean_tile_body         the tile step; hf2d_lean_tile and its _fx (fused
-//                          exchange), _tr (phase trace), _nt (128 / 64 threads)
-//                          and _occ (register budget) forms
+//                          exchange), _tr (phase trace) and _nt (128 / 64
+//                          threads) forms
 // The fused exchange's types and device functions are in dev_common.hpp.
 // Included by step_tile.hip only.
 #pragma once
@@ -302,12 +302,5 @@ __global__ __launch_bounds__(NT) void hf2d_lean_tile_tr_nt(StepParams P, LeanSoA
                                                           ResidualPack* partials, unsigned long long* trace) {
   lean_tile_body<false, false, true, CPT, false, true, NT>(P, L, T, sc, slot, slot_next, serial, partials, FusedX{},
                                                            trace);
-}
-
-template <bool RES, bool OUT, bool SG, int OCC, int CPT = 1>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(OCC)))
-void hf2d_lean_tile_occ(StepParams P, LeanSoA L, LeanTile T, DevScalars* sc, int slot, int slot_next, int serial,
-                        ResidualPack* partials) {
-  lean_tile_body<RES, OUT, SG, CPT>(P, L, T, sc, slot, slot_next, serial, partials);
 }
 }  // namespace hf2d

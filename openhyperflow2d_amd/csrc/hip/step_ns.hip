@@ -1295,13 +1295,12 @@ DeviceSolver::StepDone DeviceSolver::lnm_step(const StepCtx& c) {
   // then the dt MIN (as the lean N-S and inviscid tile kernels)
   // (the decision must be the same on every rank -- the exchange sequence
   // differs -- so a strip too narrow to split runs all its tiles at once)
-  // Opt-in (lnm_overlap / HF2D_LNM_SPLIT=1): the edge part is one
+  // Opt-in (lnm_overlap): the edge part is one
   // workgroup round of ~50 tiles on an otherwise idle GPU before the interior
   // starts, so on the mailbox transport the split step measured 109 us of
   // exchange cost against 17 us for all tiles + push / unpack
   // (tools/exchange_loopback.py, scramjet 8 ranks, profiles/exchange_loopback_r05.md)
-  static const bool split_env = std::getenv("HF2D_LNM_SPLIT") && std::string(std::getenv("HF2D_LNM_SPLIT")) == "1";
-  const bool lnm_split = (split_env || lnm_overlap) && comm_overlap &&
+  const bool lnm_split = lnm_overlap && comm_overlap &&
                          (m.p2p.on ? p2p_fuse : (m.comm || m.local)) && m.nranks > 1 && !want_res &&
                          cs.cfg.isAdiabaticWall;
   const bool parts = T.nbi >= 2 + T.ne;

@@ -194,7 +194,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
   // (the decision must be the same on every rank -- the exchange sequence
   // differs -- so a strip too narrow to split runs all its tiles at once)
   const bool split = comm_overlap && !fx_step && !m.p2p.on && (m.comm || m.local) && m.nranks > 1 &&
-                     !want_res && !out && !tile_trace && lean_occ == 0;
+                     !want_res && !out && !tile_trace;
   if (split) {
     lean_tile_last.seen |= 1;   // (the part launches are plain steps)
     lean_T_stored = false;
@@ -238,12 +238,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
                        slot_next, serial, m.partials, fx_device(X));
     dt_word_valid = word;
     fx_pending = true;   // exchanged inside the tile kernel
-  } else if (sg && cpt == 1 && var == 0 && lean_occ == 6 && !tile_trace && nt == BLOCK)
-    hipLaunchKernelGGL((hf2d_lean_tile_occ<false, false, true, 6>), dim3(ntile), dim3(BLOCK), shmem, st, P, L, T,
-                       m.sc, slot, slot_next, serial, m.partials);
-  // (multi-gas, one cell per thread, at a 5-wave register budget -- 96
-  // VGPRs + 10 spilled instead of 103: the triple point ran 351 -> 365 us)
-  else {
+  } else {
     // single GPU, last step of the host call: the scalars go to the host
     // mirror from the kernel's own tail (host_tail)
     const bool mirror = var == 1 && step_outputs && !tile_trace && host_tail && m.nranks == 1 && !m.local && !m.p2p.on;

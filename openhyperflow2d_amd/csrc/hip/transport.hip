@@ -768,8 +768,9 @@ FusedX DeviceSolver::fused_args() const {
 void DeviceSolver::p2p_push(const ColList& L, void* on_stream, int dt_slot, int fold_dt, int finish) {
   Impl& m = *impl;
   const int cnt = L.nf * h.ny;
-  hipLaunchKernelGGL(push_kernel(push_per), dim3(push_grid(push_per, cnt)), dim3(BLOCK), 0, (hipStream_t)on_stream, L,
-                     l_off, l_off + (gi1 - gi0) - 1, h.ny, cnt, fused_args(), m.sc, dt_slot, fold_dt, finish);
+  hipLaunchKernelGGL(hf2d_p2p_push, dim3((unsigned)std::max(1, (2 * cnt + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                     (hipStream_t)on_stream, L, l_off, l_off + (gi1 - gi0) - 1, h.ny, cnt, fused_args(), m.sc, dt_slot,
+                     fold_dt, finish);
   HIP_CHECK(hipGetLastError());
 }
 

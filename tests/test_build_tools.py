@@ -48,6 +48,36 @@ def test_every_kernel_is_compiled_in_one_code_object(native):
     assert len(kr.resources(native.__file__)) == sum(len(o) for o in objs)
 
 
+def test_readme_knobs_are_the_ones_the_code_reads():
+    """The README's "Device tuning knobs" paragraph and the code agree: every HF2D_*
+    variable named there is read somewhere in the package or in bench.py, and every
+    getenv("HF2D_...") of the native sources is named in the README."""
+    import re
+
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    start = readme.index("Device tuning knobs")
+    named = set(re.findall(r"HF2D_[A-Z0-9_]+", readme[start:readme.index("\n\n", start)]))
+    assert len(named) > 10, named
+    pkg = os.path.join(ROOT, "openhyperflow2d_amd")
+    texts = {os.path.join(ROOT, "bench.py"): open(os.path.join(ROOT, "bench.py")).read()}
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith((".py", ".cpp", ".hpp", ".hip", ".inc", ".sh")):
+                texts[os.path.join(d, f)] = open(os.path.join(d, f), errors="replace").read()
+    reads = set()
+    for t in texts.values():
+        reads |= set(re.findall(r"""(?:getenv\(|environ\.get\(|environ\[)\s*["'](HF2D_[A-Z0-9_]+)["']""", t))
+    assert named - reads == set(), "named in the README, read nowhere"
+    csrc = os.path.join(pkg, "csrc") + os.sep
+    native_reads = set()
+    for p, t in texts.items():
+        if p.startswith(csrc):
+            native_reads |= set(re.findall(r'getenv\("(HF2D_[A-Z0-9_]+)"', t))
+    assert native_reads, "no getenv found in the native sources"
+    everywhere = set(re.findall(r"HF2D_[A-Z0-9_]+", readme))
+    assert native_reads - everywhere == set(), "read by the native code, not in the README"
+
+
 def test_plot_helpers_write_gnuplot_scripts(native, tmp_path):
     deck = os.path.join(ROOT, "tests", "fixtures", "ref", "wedge15_200x40_euler", "deck.dat")
     shutil.copy(deck, tmp_path / "deck.dat")

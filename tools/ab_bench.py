@@ -35,8 +35,6 @@ def main():
             s.solver.lean_sg = False
         elif v0.startswith("cpt"):
             s.solver.lean_cpt = int(v0[3:])
-        elif v0.startswith("occ"):
-            s.solver.lean_occ = int(v0[3:])
         elif v0.startswith("tj"):
             s.solver.lean_tj = int(v0[2:])
         elif v0 == "flat":
