@@ -25,6 +25,9 @@ using namespace hf2d;
 
 namespace {
 
+// environment column of DeviceSolver.knob_table(): the variable's name, or None
+py::object knob_env(const char* var) { return var ? py::object(py::str(var)) : py::object(py::none()); }
+
 // Comm whose reductions are delegated to Python callables (gloo tests).
 struct PyComm : Comm {
   int r = 0, n = 1;
@@ -917,33 +920,62 @@ PYBIND11_MODULE(_hf2d, m) {
                   py::arg("blobs"), py::arg("rank"))
       .def("p2p_fallback", &DeviceSolver::p2p_fallback, py::call_guard<py::gil_scoped_release>())
       .def_property("p2p_active", &DeviceSolver::p2p_active, &DeviceSolver::p2p_set)
-      .def_readwrite("p2p_fuse", &DeviceSolver::p2p_fuse)
-      .def_readwrite("p2p_queue_check", &DeviceSolver::p2p_queue_check)
-      .def_readwrite("dt_read_mode", &DeviceSolver::dt_read_mode)
-      .def_readwrite("tile_skip_same", &DeviceSolver::tile_skip_same)
-      .def_readwrite("lns_ghost_prologue", &DeviceSolver::lns_ghost_prologue)
-      .def_readonly("lns_prologue_steps", &DeviceSolver::lns_prologue_steps)
-      .def_readwrite("fill_occ", &DeviceSolver::fill_occ)
-      .def_readwrite("split_xcd", &DeviceSolver::split_xcd)
-      .def_readwrite("grad_every", &DeviceSolver::grad_every)
-      .def_readwrite("chem_compact", &DeviceSolver::chem_compact)
-      .def_readwrite("comm_overlap", &DeviceSolver::comm_overlap)
-      .def_readwrite("lnm_overlap", &DeviceSolver::lnm_overlap)
-      .def_readwrite("host_tail", &DeviceSolver::host_tail)
-      .def_readwrite("lean_ns", &DeviceSolver::lean_ns)
-      .def_readwrite("lns_occ", &DeviceSolver::lns_occ)
+      // the tuning knobs: one read-write attribute per row of hip/device_knobs.hpp
+#define HF2D_KNOB_BIND(name, type, def, env, graph) .def_readwrite(#name, &DeviceSolver::name)
+      HF2D_DEVICE_KNOBS(HF2D_KNOB_BIND)
+#undef HF2D_KNOB_BIND
+      .def_static("knob_table",
+                  []() {
+                    py::list rows;
+#define HF2D_KNOB_ROW(name, type, def, env, graph) \
+  rows.append(py::make_tuple(#name, #type, (type)(def), knob_env(env), (bool)(graph)));
+                    HF2D_DEVICE_KNOBS(HF2D_KNOB_ROW)
+#undef HF2D_KNOB_ROW
+                    return rows;
+                  },
+                  "one (name, type, default, environment variable or None, graph) tuple per tuning knob")
+      .def_static("knobs_from_env",
+                  []() {
+                    DeviceKnobs k;
+                    k.read_env();
+                    py::dict d;
+#define HF2D_KNOB_VALUE(name, type, def, env, graph) d[#name] = k.name;
+                    HF2D_DEVICE_KNOBS(HF2D_KNOB_VALUE)
+#undef HF2D_KNOB_VALUE
+                    return d;
+                  },
+                  "{name: value} of the knobs a solver constructed now would start with (no GPU needed)")
+      // results (read-only): what construction / upload found eligible
+      .def_readonly("lean_ok", &DeviceSolver::lean_ok)
+      .def_readonly("lean_why", &DeviceSolver::lean_why)
+      .def_readonly("lean_sg_ok", &DeviceSolver::lean_sg_ok)
+      .def_readonly("lean_has_cauchy_x", &DeviceSolver::lean_has_cauchy_x)
+      .def_readonly("any_cauchy_x", &DeviceSolver::any_cauchy_x)
+      .def_readonly("sgl_ok", &DeviceSolver::sgl_ok)
+      .def_readonly("sgl_why", &DeviceSolver::sgl_why)
+      .def_readonly("sk_mode", &DeviceSolver::sk_mode)
       .def_readonly("lns_ok", &DeviceSolver::lns_ok)
       .def_readonly("lns_why", &DeviceSolver::lns_why)
-      .def_readonly("lns_state", &DeviceSolver::lns_state)
-      .def_readonly("lns_steps", &DeviceSolver::lns_steps)
       .def_readonly("lns_turb", &DeviceSolver::lns_turb)
-      .def_readwrite("lean_mech", &DeviceSolver::lean_mech)
       .def_readonly("lnm_ok", &DeviceSolver::lnm_ok)
       .def_readonly("lnm_why", &DeviceSolver::lnm_why)
       .def_readonly("lnm_turb", &DeviceSolver::lnm_turb)
+      .def_readonly("chem_fast_ok", &DeviceSolver::chem_fast_ok)
+      .def_readonly("chem_rtc_ok", &DeviceSolver::chem_rtc_ok)
+      .def_readonly("chem_rtc_why", &DeviceSolver::chem_rtc_why)
+      .def_readonly("chem_kernel_used", &DeviceSolver::chem_kernel_used)
+      // counters and state (read-only)
+      .def_readonly("lns_steps", &DeviceSolver::lns_steps)
       .def_readonly("lnm_steps", &DeviceSolver::lnm_steps)
-      .def_readwrite("lnm_ti", &DeviceSolver::lnm_ti)
-      .def_readwrite("lnm_timing", &DeviceSolver::lnm_timing)
+      .def_readonly("lns_fx_steps", &DeviceSolver::lns_fx_steps)
+      .def_readonly("lns_prologue_steps", &DeviceSolver::lns_prologue_steps)
+      .def_readonly("p2p_mwg_exchanges", &DeviceSolver::p2p_mwg_exchanges)
+      .def_readonly("overlap_steps", &DeviceSolver::overlap_steps)
+      .def_readonly("graph_launches", &DeviceSolver::graph_launches)
+      .def_readonly("graph_captures", &DeviceSolver::graph_captures)
+      .def_readonly("lns_state", &DeviceSolver::lns_state)
+      .def_readonly("gi0", &DeviceSolver::gi0)
+      .def_readonly("gi1", &DeviceSolver::gi1)
       .def_property(
           "lnm_phase_ms",
           [](const DeviceSolver& s) {
@@ -953,9 +985,6 @@ PYBIND11_MODULE(_hf2d, m) {
             for (int q = 0; q < 4; q++) s.lnm_phase_ms[q] = q < (int)v.size() ? v[q] : 0.0;
           })
       .def("lnm_trace_fetch", &DeviceSolver::lnm_trace_fetch, py::call_guard<py::gil_scoped_release>())
-      .def_readonly("overlap_steps", &DeviceSolver::overlap_steps)
-      .def_readonly("lns_fx_steps", &DeviceSolver::lns_fx_steps)
-      .def_readonly("p2p_mwg_exchanges", &DeviceSolver::p2p_mwg_exchanges)
       .def("comm_rank", &DeviceSolver::comm_rank)
       .def("comm_size", &DeviceSolver::comm_size)
       .def("synchronize", &DeviceSolver::synchronize, py::call_guard<py::gil_scoped_release>())
@@ -963,26 +992,6 @@ PYBIND11_MODULE(_hf2d, m) {
       .def("trace_tile", &DeviceSolver::trace_tile, py::arg("steps") = 20,
            "one phase-traced lean tile step: per workgroup [entry, staged, wave0 computed, reduced, dt atomic done "
            "(s_memrealtime, 100 MHz), HW_ID, XCC_ID, blockIdx]")
-      .def_readwrite("fused", &DeviceSolver::fused)
-      .def_readwrite("lean", &DeviceSolver::lean)
-      .def_readwrite("lean_tile", &DeviceSolver::lean_tile)
-      .def_readwrite("lean_sg", &DeviceSolver::lean_sg)
-      .def_readwrite("lean_tj", &DeviceSolver::lean_tj)
-      .def_readwrite("tile_stagger", &DeviceSolver::tile_stagger)
-      .def_readwrite("lean_wgcu", &DeviceSolver::lean_wgcu)
-      .def_readwrite("use_graph", &DeviceSolver::use_graph)
-      .def_readwrite("chem_fast", &DeviceSolver::chem_fast)
-      .def_readwrite("chem_kernel", &DeviceSolver::chem_kernel)
-      .def_readwrite("chem_rtc", &DeviceSolver::chem_rtc)
-      .def_readonly("chem_rtc_ok", &DeviceSolver::chem_rtc_ok)
-      .def_readonly("chem_rtc_why", &DeviceSolver::chem_rtc_why)
-      .def_readonly("chem_kernel_used", &DeviceSolver::chem_kernel_used)
-      .def_readonly("chem_fast_ok", &DeviceSolver::chem_fast_ok)
-      .def_readonly("graph_launches", &DeviceSolver::graph_launches)
-      .def_readonly("graph_captures", &DeviceSolver::graph_captures)
-      .def_readwrite("lean_cpt", &DeviceSolver::lean_cpt)
-      .def_readwrite("lean_nt", &DeviceSolver::lean_nt)
-      .def_readwrite("cu_count", &DeviceSolver::cu_count)
       .def_property_readonly("lean_tile_last",
                              [](const DeviceSolver& s) {
                                const DeviceSolver::TileLast& t = s.lean_tile_last;
@@ -1002,14 +1011,6 @@ PYBIND11_MODULE(_hf2d, m) {
                              },
                              "geometry and variant (0 plain, 1 outputs, 2 residual) of the last lean tile launch; "
                              "nt == 0 after a step on any other kernel")
-      .def_readwrite("sgl", &DeviceSolver::sgl)
-      .def_readonly("sgl_ok", &DeviceSolver::sgl_ok)
-      .def_readonly("sgl_why", &DeviceSolver::sgl_why)
-      .def_readonly("sk_mode", &DeviceSolver::sk_mode)
-      .def_readonly("lean_sg_ok", &DeviceSolver::lean_sg_ok)
-      .def_readonly("lean_has_cauchy_x", &DeviceSolver::lean_has_cauchy_x)
-      .def_readwrite("halo_compact", &DeviceSolver::halo_compact)
-      .def_readonly("any_cauchy_x", &DeviceSolver::any_cauchy_x)
       .def("halo_field_count", [](const DeviceSolver& d, int group, bool full) {
         std::vector<real*> f;
         d.halo_fields(group, f, full);
@@ -1017,9 +1018,5 @@ PYBIND11_MODULE(_hf2d, m) {
       }, py::arg("group"), py::arg("full") = false)
       .def_property("lean_plain", [](const DeviceSolver& d) { return d.lean_plain; },
                     [](DeviceSolver& d, bool on) { d.set_lean_plain(on); })
-      .def_readonly("lean_ok", &DeviceSolver::lean_ok)
-      .def_readonly("lean_why", &DeviceSolver::lean_why)
-      .def_readonly("gi0", &DeviceSolver::gi0)
-      .def_readonly("gi1", &DeviceSolver::gi1)
       .def_property_readonly("stream", [](const DeviceSolver& s) { return (uintptr_t)s.stream(); });
 }

@@ -20,6 +20,8 @@
 //                       mailbox kernels (hf2d_p2p_*); RCCL and in-process transports
 //   observe.hip         monitors, probe_history.hpp (per-step recorder),
 //                       flow_stats.hpp (time-averaged flow statistics)
+//   device_knobs.hpp    the tuning knobs, one row each: members, environment reads,
+//                       Python attributes and mode_signature() are expanded from it
 //   device_impl.hpp     DeviceSolver::Impl, DevBuf, HIP_CHECK: what the units share
 //   solver_args.hpp     plain argument blocks of the lean N-S / mechanism steps
 //                       and the recorder (types only)
@@ -88,17 +90,7 @@ DeviceSolver::DeviceSolver(Case& c, int device, int gi0_, int gi1_) : SolverBase
     HIP_CHECK(hipGetDeviceProperties(&prop, dev));
     cu_count = prop.multiProcessorCount;
   }
-  if (const char* e = std::getenv("HF2D_SPLIT_XCD")) split_xcd = std::string(e) != "0";
-  if (const char* e = std::getenv("HF2D_SPLIT_XCD_MECH")) split_xcd_mech = std::string(e) != "0";
-  if (const char* e = std::getenv("HF2D_MECH_LAZY")) mech_lazy = std::string(e) != "0";
-  if (const char* e = std::getenv("HF2D_CHEM_KERNEL")) chem_kernel = std::atoi(e);   // 1 compiled 2 MFMA 3 generic 4 hiprtc
-  if (const char* e = std::getenv("HF2D_GRAD_EVERY")) grad_every = std::string(e) != "0";
-  if (const char* e = std::getenv("HF2D_LNM_TI")) lnm_ti = std::atoi(e);
-  if (const char* e = std::getenv("HF2D_STAGGER")) tile_stagger = std::atoi(e);
-  if (const char* e = std::getenv("HF2D_HOST_TAIL")) host_tail = std::string(e) != "0";
-  if (const char* e = std::getenv("HF2D_DT_READ")) dt_read_mode = std::atoi(e);
-  if (const char* e = std::getenv("HF2D_SKIP_SAME")) tile_skip_same = std::string(e) != "0";
-  if (const char* e = std::getenv("HF2D_GHOST_PROLOGUE")) lns_ghost_prologue = std::string(e) != "0";
+  read_env();
   gi0 = gi0_;
   gi1 = gi1_ < 0 ? c.J.nx : gi1_;
   // ghost columns: N-S strips keep two (the lean N-S / mechanism tiles
@@ -606,19 +598,21 @@ uint64_t DeviceSolver::mode_signature() const {
   // flips only some of them, so a window cached before a download must not
   // replay after it -- it did, and the lean mechanism run then stepped on
   // the previous level's buffers from the first replayed window on)
-  const int fields[] = {lean_state, (int)lean, (int)fused, (int)lean_tile, (int)(lean_sg && lean_sg_ok), lean_cpt,
-                        lean_tj, lean_nt, lean_wgcu, (int)(p2p_fuse && impl->p2p.on), (int)(sgl && sgl_ok), lns_state,
-                        (int)lean_ns, (int)lean_mech, sbuf, abuf, dsbuf, pbuf, cbuf,
-                        // (settings a captured launch bakes in: the cpt gate and the stagger rounds,
-                        // the dt read, the skipped stores, the ghost prologue)
-                        cu_count, dt_read_mode, (int)tile_skip_same, (int)lns_ghost_prologue,
-                        // (a window captured before record_probes has no recorder launch, one
-                        // captured before arming again writes the previous ring)
-                        probe_gen,
-                        // (likewise the accumulator's two launches: start / stop_averaging)
-                        stats_gen};
   uint64_t h = 0;
-  for (int f : fields) h = h * 1000003ull + (uint64_t)(f + 1);
+  auto mix = [&](int f) { h = h * 1000003ull + (uint64_t)(f + 1); };
+  // every knob a captured launch bakes in (the `graph` rows of device_knobs.hpp)
+#define HF2D_KNOB_MIX(name, type, def, env, graph) \
+  if (graph) mix((int)name);
+  HF2D_DEVICE_KNOBS(HF2D_KNOB_MIX)
+#undef HF2D_KNOB_MIX
+  // and the state that is not a knob
+  const int state[] = {lean_state, lns_state, sbuf, abuf, dsbuf, pbuf, cbuf, (int)(p2p_fuse && impl->p2p.on),
+                       // (a window captured before record_probes has no recorder launch, one
+                       // captured before arming again writes the previous ring)
+                       probe_gen,
+                       // (likewise the accumulator's two launches: start / stop_averaging)
+                       stats_gen};
+  for (int f : state) mix(f);
   return h;
 }
 
@@ -1009,10 +1003,7 @@ std::unique_ptr<SolverBase> make_gpu_strip_solver(Case& cs, int device, int gi0,
   if (device >= ndev && ndev > 0) device %= ndev;
   std::unique_ptr<DeviceSolver> s(new DeviceSolver(cs, device < 0 ? 0 : device, gi0, gi1));
   used = "none";
-  if (cs.cfg.ThreadBlockSize == 0) {
-    const char* at = std::getenv("HF2D_AUTOTUNE");
-    if (!at || std::string(at) != "0") s->autotune();
-  }
+  if (cs.cfg.ThreadBlockSize == 0 && s->autotune_enabled) s->autotune();
   if (boot.size() == 1) return std::unique_ptr<SolverBase>(s.release());
   const int r = boot.rank(), n = boot.size();
   auto use_rccl = [&] {
@@ -1054,8 +1045,7 @@ std::unique_ptr<SolverBase> make_gpu_strip_solver(Case& cs, int device, int gi0,
   }
   if (boot.allreduce_max_int(bad) == 0) {
     used = "p2p";
-    const char* f = std::getenv("HF2D_P2P_FUSE");
-    s->p2p_fuse = !(f && std::string(f) == "0");
+    s->p2p_fuse = s->p2p_fuse_wanted;
   } else {
     use_rccl();
     s->p2p_fallback();

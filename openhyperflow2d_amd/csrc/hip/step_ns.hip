@@ -1277,7 +1277,7 @@ DeviceSolver::StepDone DeviceSolver::lnm_step(const StepCtx& c) {
     return d;
   }
   LnmArrays a = m.lnm_arrays(h, sbuf, pbuf, cbuf, dsbuf, abuf);
-  if (std::getenv("HF2D_LNM_TRACE")) {   // phase trace of every step (the last one is kept)
+  if (lnm_trace) {   // phase trace of every step (the last one is kept)
     const long nwg = (long)((P.i1 - P.i0 + lnm_ti - 1) / lnm_ti) * ((P.ny + LNM_TILE - 1) / LNM_TILE);
     if (!m.lnm_trace || m.lnm_trace_n < nwg) {
       m.lnm_trace = m.mem.alloc<unsigned long long>(nwg * 12);

@@ -751,12 +751,9 @@ FusedX DeviceSolver::fused_args() const {
   X.nranks = m.nranks;
   X.sides = (has_left ? 1 : 0) | (has_right ? 2 : 0);
   X.on = 1;
-  static const int skip = std::getenv("HF2D_FX_SKIP") ? std::atoi(std::getenv("HF2D_FX_SKIP")) : 0;
-  X.skip = m.p2p.loop ? skip : 0;   // (loopback timing runs only)
-  static const int ef = std::getenv("HF2D_FX_EDGE_FIRST") ? std::atoi(std::getenv("HF2D_FX_EDGE_FIRST")) : 0;
-  static const int c1 = std::getenv("HF2D_FX_COUNT1") ? std::atoi(std::getenv("HF2D_FX_COUNT1")) : 0;
-  X.edge_first = ef;
-  X.count1 = c1;
+  X.skip = m.p2p.loop ? fx_skip : 0;   // (loopback timing runs only)
+  X.edge_first = fx_edge_first;
+  X.count1 = fx_count1;
   return X;
 }
 

@@ -16,8 +16,9 @@ import numpy as np
 def maybe_autotune(case, solver) -> str:
     """Deck key ThreadBlockSize = 0 (the reference's "auto-calibrate") tunes
     the lean kernel geometry on the device before the first step
-    (DeviceSolver.autotune; results are unaffected).  HF2D_AUTOTUNE=0 skips."""
-    if case.thread_block_size != 0 or os.environ.get("HF2D_AUTOTUNE", "1") == "0":
+    (DeviceSolver.autotune; results are unaffected).  HF2D_AUTOTUNE=0 skips
+    (the solver's autotune_enabled knob, read when it was constructed)."""
+    if case.thread_block_size != 0 or not solver.autotune_enabled:
         return ""
     return solver.autotune()
 

@@ -186,10 +186,10 @@ class DistributedSimulation:
             self.p2p_validated = True
             # the exchange is folded into the tile kernels (the last workgroup
             # publishes and waits, one peer per lane); HF2D_P2P_FUSE=0 selects a
-            # separate exchange kernel.  Device-side cost per step without a
-            # second strip on the GPU: tools/exchange_loopback.py
-            # (profiles/exchange_loopback_r05.md)
-            s.p2p_fuse = os.environ.get("HF2D_P2P_FUSE", "1") == "1"
+            # separate exchange kernel (the solver's p2p_fuse_wanted knob).
+            # Device-side cost per step without a second strip on the GPU:
+            # tools/exchange_loopback.py (profiles/exchange_loopback_r05.md)
+            s.p2p_fuse = s.p2p_fuse_wanted
         else:
             if not nccl:
                 obj = [self.hf.DeviceSolver.nccl_unique_id() if rank == 0 else None]

@@ -308,3 +308,61 @@ def test_graph_windows_follow_changed_settings(gpu, monkeypatch):
         np.testing.assert_array_equal(a.field(f), b.field(f), err_msg=f)
         np.testing.assert_array_equal(a.field(f), c.field(f), err_msg=f)
     _assert_equal(a.field, a.summary(), _cpu_reference(text, tuple(calls))[-1], False)
+
+
+def test_graph_windows_follow_a_knob_the_old_list_missed(gpu, monkeypatch):
+    """tile_stagger is an argument of the captured tile launches (every `graph`
+    row of the knob table is part of DeviceSolver::mode_signature): after it
+    changes, exactly one window is captured anew and carries the new start
+    delay, and the run equals a solver that had it from the start bit for bit."""
+    text = decks.wedge15(221, 41, **BIG)
+    a, b = [_gpu(gpu, monkeypatch, text) for _ in range(2)]
+    for r in (a, b):
+        r.solver.use_graph = True
+        r.solver.lean_nt, r.solver.lean_cpt, r.solver.lean_tj = 256, 2, 0
+        r.solver.cu_count = 8   # 20 two-cell tiles: at least two per CU, at most four rounds (the stagger gate)
+    a.solver.tile_stagger = 0
+    b.solver.tile_stagger = 150
+    for r in (a, b):
+        r.step(24)
+    caps = [r.solver.graph_captures for r in (a, b)]
+    assert min(caps) > 0 and a.solver.graph_launches > caps[0], (caps, a.solver.graph_launches)
+    assert a.solver.lean_tile_last["stagger"] == 0 and b.solver.lean_tile_last["stagger"] == 150
+    a.solver.tile_stagger = 150
+    for r in (a, b):
+        r.step(24)
+    assert a.solver.graph_captures == caps[0] + 1, a.solver.graph_captures
+    assert b.solver.graph_captures == caps[1]   # unchanged settings: replays
+    assert a.solver.lean_tile_last["stagger"] == 150, a.solver.lean_tile_last
+    assert (a.solver.lean_tile_last["nt"], a.solver.lean_tile_last["cpt"]) == (256, 2)
+    assert a.summary()["dt"] == b.summary()["dt"]
+    for f in FIELDS:
+        np.testing.assert_array_equal(a.field(f), b.field(f), err_msg=f)
+
+
+def test_graph_windows_follow_fill_occ_on_the_split_path(gpu, monkeypatch):
+    """The split predict / fill steps in step graphs (laminar step, 37 x 23,
+    lean N-S off): fill_occ selects the fill kernel's pointer, so a change
+    captures exactly one window anew, and the run equals a twin that had
+    fill_occ = 2 from the start bit for bit."""
+    text = decks.step(37, 23, **BIG)
+    a, b = [_gpu(gpu, monkeypatch, text) for _ in range(2)]
+    for r in (a, b):
+        r.solver.lean_ns = False
+        r.solver.use_graph = True
+    assert a.solver.fill_occ == -1
+    b.solver.fill_occ = 2
+    for r in (a, b):
+        r.step(24)
+    caps = [r.solver.graph_captures for r in (a, b)]
+    assert min(caps) > 0 and a.solver.graph_launches > caps[0], (caps, a.solver.graph_launches)
+    assert a.solver.lns_steps == 0 and b.solver.lns_steps == 0
+    a.solver.fill_occ = 2
+    for r in (a, b):
+        r.step(24)
+    assert a.solver.graph_captures == caps[0] + 1, a.solver.graph_captures
+    assert b.solver.graph_captures == caps[1]   # unchanged settings: replays
+    assert a.solver.lns_steps == 0 and b.solver.lns_steps == 0
+    assert a.summary()["dt"] == b.summary()["dt"]
+    for f in NS_FIELDS:
+        np.testing.assert_array_equal(a.field(f), b.field(f), err_msg=f)
