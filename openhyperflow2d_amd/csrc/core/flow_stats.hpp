@@ -23,7 +23,7 @@ constexpr int STATS_VARS = 5;   // p, T, rho, U, V (the probe recorder's row)
 struct StatsScalars {
   double W = 0.0;        // weight sum: the averaged time span (weight = time) or the sample count
   double t_seen = 0.0;   // clock at the last sample (at arming / reset / upload before the first)
-  double t_off = 0.0;    // device: the clock is DevScalars::time_part - t_off (upload() restarts time_part)
+  double t_off = 0.0;    // device: the clock is DevScalars::time_part - t_off (upload() and a cycle roll restart time_part)
   double w = 0.0, r = 0.0;   // this step's weight and w / W
   unsigned long long samples = 0, seen = 0;   // samples taken, steps seen since arming / reset
   int sample = 0;        // this step is a sample (the cell pass reads it)

@@ -500,7 +500,42 @@ void DeviceSolver::download(Field& J) {
   h.mech_to_case(cs, gi0 - l_off, l_off, l_off + (gi1 - gi0), 0);
 }
 
-void DeviceSolver::on_cycle_roll() { time_offset = last_dev_time; }
+// The driver folded cur_time_part into global_time and restarts it at 0: the
+// device's time_part restarts with it, so that the host's cur_time_part stays
+// the plain sum of this cycle's dt -- bit for bit the CPU stepper's -- and not
+// the difference of two running sums (one ulp off after the first cycle
+// boundary).  The two clocks derived from time_part move with it: the probe
+// recorder's stored times (probe_history() converts rows of earlier cycles as
+// before) and the accumulator's offset (its clock goes on unbroken).
+// Always called right after sync_scalars(), with no step in between:
+// last_dev_time is the device's time_part now.
+void DeviceSolver::on_cycle_roll() {
+  Impl& m = *impl;
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  const double T = last_dev_time;
+  const double zero = 0.0;
+  HIP_CHECK(hipMemcpyAsync(&m.sc->time_part, &zero, sizeof zero, hipMemcpyHostToDevice, m.stream));
+  if (probe_cap) {
+    std::vector<double> tp((size_t)m.ring.cap);
+    HIP_CHECK(hipMemcpyAsync(tp.data(), m.ring.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    for (double& t : tp) t -= T;
+    HIP_CHECK(hipMemcpyAsync(m.ring.times, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+  }
+  if (stats_armed) {
+    double off = 0.0;
+    HIP_CHECK(hipMemcpyAsync(&off, &m.stats.sc->t_off, sizeof off, hipMemcpyDeviceToHost, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    off -= T;
+    HIP_CHECK(hipMemcpyAsync(&m.stats.sc->t_off, &off, sizeof off, hipMemcpyHostToDevice, m.stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  m.sc_host->time_part = 0.0;
+  time_offset = 0.0;
+  last_dev_time = 0.0;
+}
 
 void DeviceSolver::poison_cell(int gi, int j) {
   flush_pending();

@@ -129,7 +129,8 @@ ProbeHistory DeviceSolver::probe_history() {
   H.values.resize((size_t)n * row);
   for (long k = 0; k < n; k++) {
     const long s = (first + k) % cap;
-    // the device accumulates time since the start; the host's time is
+    // the device accumulates time since the cycle start (on_cycle_roll moved
+    // the rows of earlier cycles with it); the host's time is
     // global_time + (time_part - time_offset) (sync_scalars, summary)
     const real part = tp[s] - time_offset;
     H.times[k] = cs.global_time + part;

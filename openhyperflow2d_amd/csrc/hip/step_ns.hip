@@ -497,6 +497,10 @@ void DeviceSolver::cycle_update() {
       const unsigned nb = (unsigned)((c1 - c0 + BLOCK - 1) / BLOCK);
       hipLaunchKernelGGL(hf2d_yplus, dim3(nb), dim3(BLOCK), 0, m.stream, s, c0, c1, m.uw_all, m.uw_all_ok);
       HIP_CHECK(hipGetLastError());
+      // (uw and ok are pageable and end with this block: the two copies must
+      // have read them before that -- a copy still queued then uploaded freed
+      // memory, and with ok = 0 everywhere y+ stayed what it was)
+      HIP_CHECK(hipStreamSynchronize(m.stream));
     }
   }
   HIP_CHECK(hipStreamSynchronize(m.stream));
