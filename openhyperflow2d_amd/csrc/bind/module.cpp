@@ -561,6 +561,9 @@ PYBIND11_MODULE(_hf2d, m) {
       },
       py::arg("ncols"), py::arg("ny"), py::arg("block"), py::arg("tj") = 0, py::arg("cpt") = 1,
       "lean tile geometry (lean_euler.hpp LeanTile) of a strip of ncols x ny cells");
+  m.def("lean_tile_stage_kmax", &lean_tile_stage_kmax, py::arg("nt"), py::arg("cpt"),
+        "largest slots per thread (ceil(NC / nt)) the single-gas lean tile kernel stages in one batch of loads; "
+        "beyond it the kernel runs the staging loop (lean_tile_last['stage'] == 0)");
   m.def("sk_eligible", [](const Case& c) { std::string w; const int md = sk_eligible(c, &w); return py::make_tuple(md, w); },
         py::arg("case"), "split-kernel specialisation (0 generic, 1 single-gas laminar, 2 single-gas turbulent; reason)");
   m.def("smooth", [](py::array_t<double, py::array::c_style> a, int axis) {
@@ -1007,6 +1010,7 @@ PYBIND11_MODULE(_hf2d, m) {
                                d["var"] = t.var;
                                d["seen"] = t.seen;
                                d["dt_read"] = t.dt_read;
+                               d["stage"] = t.stage;
                                return d;
                              },
                              "geometry and variant (0 plain, 1 outputs, 2 residual) of the last lean tile launch; "

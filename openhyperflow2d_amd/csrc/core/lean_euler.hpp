@@ -136,6 +136,25 @@ HF_HD inline void lean_load_own(const LeanSoA& L, long idx, LeanOwn& o) {
   }
 }
 
+// lean_load_own in two parts, for a caller that issues other loads between
+// the flags and the values that wait for them (lean_tile.hpp).
+HF_HD inline void lean_load_own_flags(const LeanSoA& L, long idx, LeanOwn& o) {
+  o.CT = L.CT[idx];
+  o.lb = L.lb[idx];
+}
+template <int NE = 4 + NCOMP>
+HF_HD inline void lean_load_own_rest(const LeanSoA& L, long idx, LeanOwn& o) {
+  const long N = L.N;
+  o.filled = !has_all(o.CT, CT_SOLID) && has_all(o.CT, CT_NODE_IS_SET);
+  if (o.filled) {
+#pragma unroll
+    for (int k = 0; k < NE; k++) o.beta[k] = L.beta[k * N + idx];
+    o.CP = L.CP[idx];
+    o.R = L.R[idx];
+    o.kk = L.kk[idx];
+  }
+}
+
 // Accessor members shared by the global-memory and the LDS-tile IO: the
 // node's own persistent arrays (beta, dS/dx, dS/dy, SrcAdd) stay in global
 // memory, addressed by the global indices idx / iL / iR / iU / iD.
@@ -434,6 +453,9 @@ struct LeanTile {
   // comm-overlap launches: tile columns at the strip's right edge in the edge
   // part (2 when the last one holds a single column and the halo carries two)
   int ne = 1;
+  // device single-gas kernels: slots per thread of the batched staging
+  // (lean_tile.hpp), 0: the loop of lean_tile_stage
+  int stage = 0;
 };
 
 // Tile height: tj > 0 overrides (clamped to [LEAN_TILE_MIN_TJ, block]);

@@ -129,6 +129,39 @@ __device__ inline void apply_dt(StepParams& P, const DevScalars* sc, int slot, b
   }
 }
 
+// apply_dt(tile) of the single-gas lean tile kernels in two parts, so that the
+// dt read is in flight while the kernel issues its other loads: dt_tile_issue
+// starts it (dt_read 1: this lane's word of dt_get_wave, not yet reduced;
+// otherwise the slot's value), dt_tile_finish reduces it and sets P.dt and
+// the two quotients.  Every lane of the wavefront must be active in both.
+__device__ inline unsigned long long dt_tile_issue(StepParams& P, const DevScalars* sc, int slot) {
+  if (P.scen) {   // scenario values of this step's iteration (scenario_next)
+    P.beta_min = sc->beta_min[slot];
+    P.CFL_min = sc->cfl_min[slot];
+  }
+  if (__builtin_expect(P.lag_dt != 0, 0)) return sc->dt_lag[slot];
+  if (P.dt_read == 2) return sc->dt_bits[slot];
+  if (P.dt_read == 1) {
+    const int lane = (int)(threadIdx.x & 63);
+    unsigned long long b = ~0ull;
+    if (lane < DT_SHARDS) b = sc->dt_sh[slot][lane][0];
+    else if (lane == DT_SHARDS) b = sc->dt_bits[slot];
+    return b;
+  }
+  return d_to_bits(dt_get(sc, slot));
+}
+__device__ inline void dt_tile_finish(StepParams& P, unsigned long long b) {
+  if (!__builtin_expect(P.lag_dt != 0, 0) && P.dt_read == 1) {
+#pragma unroll
+    for (int off = 1; off < 32; off <<= 1) b = dt_bits_min(b, (unsigned long long)__shfl_xor((long long)b, off, 64));
+    b = (unsigned long long)__shfl((long long)b, 0, 64);
+  }
+  const double dt = bits_to_d(b);
+  P.dt = dt;
+  P.dtdx = dt / P.dx;
+  P.dtdy = dt / P.dy;
+}
+
 // Run once per step by one thread of the step's first kernel: iteration
 // number and CFL / beta scenario values (SolverBase::make_params arithmetic)
 // of the next step.
@@ -244,6 +277,13 @@ __device__ inline void p2p_store(float* p, float v) {
 // outstanding vector-memory operations of this wave (stores included on gfx9)
 // have completed: the ordering point for the relaxed system-coherent stores
 __device__ inline void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// Every bit of v stays live up to this point.  For the destination of a load
+// still in flight of which the code uses only a part: the register allocator
+// otherwise hands the unused half to a new value right away, and the write
+// to it has to wait for the load (s_waitcnt) in front of whatever was meant
+// to be issued behind it.  Place it where the load is waited for anyway.
+__device__ inline void keep_whole(u64& v) { asm volatile("" : "+v"(v)); }
 
 __device__ inline unsigned long long rt_clock() { return __builtin_amdgcn_s_memrealtime(); }
 constexpr int FX_DONE_STRIDE = 32;   // completion counters on lines of their own

@@ -20,6 +20,10 @@ struct LnmArrays;
 struct LeanTile;
 
 bool gpu_available();
+// Largest number of slots per thread that the single-gas lean tile kernel of
+// nt threads and cpt cells per thread stages in one batch (lean_tile.hpp); a
+// tile that needs more runs the staging loop.  0: no such kernel.
+int lean_tile_stage_kmax(int nt, int cpt);
 
 // In-process stand-in for the RCCL communicator: N DeviceSolvers (one host
 // thread each, possibly sharing one GPU) exchange halo buffers with D2D
@@ -192,10 +196,12 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   // 1 outputs, 2 residual; seen: bit v set for every variant v launched in
   // the unbroken run of tile steps with this nt and cpt that the last one
   // ends (the last step of a host call is never a plain one); dt_read: how
-  // it read the step's dt (StepParams::dt_read).  Tests assert through it
-  // which variant ran.
+  // it read the step's dt (StepParams::dt_read); stage: slots per thread of
+  // the batched staging, 0 for the staging loop (LeanTile::stage).  Tests
+  // assert through it which variant ran.
   struct TileLast {
     int nt = 0, cpt = 0, TI = 0, TJ = 0, nbi = 0, nbj = 0, stagger = 0, fx = 0, var = 0, seen = 0, dt_read = 0;
+    int stage = 0;
   };
   TileLast lean_tile_last;
 

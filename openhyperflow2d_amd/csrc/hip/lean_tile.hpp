@@ -73,6 +73,93 @@ constexpr int TILE_TRACE_WORDS = 8;
 #endif
 constexpr int LDS_PER_CU = 160 * 1024;
 
+// Batched staging of a single-gas tile (device form of lean_tile_stage<true>,
+// same LDS layout, same skipped slots, same values).  Thread t owns the slots
+// t, t + NT, ..., K = ceil(NC / NT) of them (LeanTile::stage, set by the host):
+// lean_stage_issue starts all K x 7 loads into registers in one unrolled
+// block, lean_stage_write stores them to LDS.  Between the two the kernel
+// issues what else it has to load, so a wave pays one round trip for its
+// staging instead of one per pass of lean_tile_stage's loop (whose trip count
+// is a run-time value: its second pass loads only after the first has
+// arrived and been written).
+// Largest K a kernel of nt threads and cpt cells per thread stages this way:
+// the largest at which every variant of it keeps the occupancy step it has
+// with the loop alone and spills nothing to scratch; beyond it the kernel runs
+// the loop.  3 for all of them: the K x 14 staging VGPRs are live where the
+// step's own arithmetic is not yet, and 42 fit under every kernel's peak (the
+// plain one-cell kernels stay at 95 VGPRs, 5 waves per SIMD); with 4 the
+// one-cell kernels go 95 -> 107 (5 -> 4 waves) and the two-cell fused-exchange
+// ones 121 -> 129 (4 -> 3), profiles/tile_stage_batch.md.  The geometries the
+// autotune picks need 2 (64 x 1 x 16, 128 x 1 x 8, 256 x 1) or 3 (256 x 2).
+__host__ __device__ constexpr int lean_stage_kmax(int nt, int cpt) {
+  (void)nt;
+  (void)cpt;
+  return 3;
+}
+constexpr int LEAN_STAGE_KTOP = 3;   // largest K lean_tile_body dispatches
+template <int KM>
+struct LeanStaged {   // (room for KM slots; a tile of K < KM uses the first K)
+  real v[KM > 0 ? KM : 1][LEAN_TILE_FIELDS_SG];
+  int c[KM > 0 ? KM : 1];   // LDS slot, < 0: not staged (halo corner, outside the grid, beyond NC)
+};
+template <int K, int NT, int KM>
+__device__ __forceinline__ void lean_stage_issue(const StepParams& P, const LeanSoA& L, const LeanTile& T, int i0,
+                                                 int j0, LeanStaged<KM>& s) {
+  static_assert(K <= KM, "slots");
+  const long N = L.N;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const int c = (int)threadIdx.x + k * NT;
+    // (the division per slot: lean_tile_stage)
+    const int ii = c / T.W - 1, jj = c - (ii + 1) * T.W - 1;
+    const bool xh = ii < 0 || ii >= T.TI, yh = jj < 0 || jj >= T.TJ;
+    const int gi = i0 + ii, gj = j0 + jj;
+    const bool skip = c >= T.NC || (xh && yh) || gi < 0 || gi >= P.nx || gj < 0 || gj >= P.ny;
+    s.c[k] = skip ? -1 : c;
+    if (!skip) {
+      const long g = (long)gi * P.ny + gj;
+#pragma unroll
+      for (int f = 0; f < 4; f++) s.v[k][f] = L.Sin[f * N + g];
+      s.v[k][4] = L.Uin[g];
+      s.v[k][5] = L.Vin[g];
+      s.v[k][6] = L.Pin[g];
+    }
+  }
+}
+template <int K, int KM>
+__device__ __forceinline__ void lean_stage_write(const LeanTile& T, const LeanStaged<KM>& s, real* lds) {
+  static_assert(K <= KM, "slots");
+#pragma unroll
+  for (int k = 0; k < K; k++)
+    if (s.c[k] >= 0)
+#pragma unroll
+      for (int f = 0; f < LEAN_TILE_FIELDS_SG; f++) lds[f * T.NC + s.c[k]] = s.v[k][f];
+}
+
+// Workgroup 0's once-per-step updates of the scalars, after P.dt is known
+// (MIRROR: the host mirror's part, host_mirror_head).
+template <bool MIRROR, bool FX>
+__device__ __forceinline__ void lean_tile_wg0_head(const StepParams& P, DevScalars* sc, int slot, int slot_next,
+                                                   const FusedX& X, unsigned long long seq_prev) {
+  if (threadIdx.x < WAVE) {
+    // lagged dt with the fold deferred (X.defer): the previous step's tail
+    // waited for the two neighbours only; the other ranks' dt of that step
+    // is folded here, one step later, by this wavefront (one peer per lane)
+    double fold = 1.0;
+    if (FX && X.defer && P.lag_dt && seq_prev > 0) {
+      bool ok;
+      fold = p2p_wait_wave(X, seq_prev, sc, [](int) { return true; }, true, (int)(seq_prev & 1), &ok);
+    }
+    if (threadIdx.x == 0) {
+      dt_reset(sc, slot_reset(slot));
+      lag_head(P, sc, slot, slot_next, fold);
+      sc->dt_bits[slot] = d_to_bits(P.dt);   // folded (later kernels of the step read the word)
+      sc->time_part += P.dt;
+      scenario_next(P, sc, slot, slot_next);
+      if (MIRROR && P.host_sc) host_mirror_head(P, sc, slot_next);
+    }
+  }
+}
 
 // NT: threads per workgroup (BLOCK, or 128 / 64 for the small strips of a
 // multi-GPU run: at 250 x 200 cells per GPU a 256-thread tiling leaves ~50 of
@@ -113,25 +200,12 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
                                           : tile_of_part(xcd_remap(blockIdx.x, gridDim.x), part, T);
   unsigned long long seq_prev = 0;
   if (FX) seq_prev = *X.seq;
-  apply_dt(P, sc, slot, true);
-  if (b == 0 && threadIdx.x < WAVE) {
-    // lagged dt with the fold deferred (X.defer): the previous step's tail
-    // waited for the two neighbours only; the other ranks' dt of that step
-    // is folded here, one step later, by this wavefront (one peer per lane)
-    double fold = 1.0;
-    if (FX && X.defer && P.lag_dt && seq_prev > 0) {
-      bool ok;
-      fold = p2p_wait_wave(X, seq_prev, sc, [](int) { return true; }, true, (int)(seq_prev & 1), &ok);
-    }
-    if (threadIdx.x == 0) {
-      dt_reset(sc, slot_reset(slot));
-      lag_head(P, sc, slot, slot_next, fold);
-      sc->dt_bits[slot] = d_to_bits(P.dt);   // folded (later kernels of the step read the word)
-      sc->time_part += P.dt;
-      scenario_next(P, sc, slot, slot_next);
-      if (OUT && !RES && !FX && P.host_sc) host_mirror_head(P, sc, slot_next);
-    }
-  }
+  // (single gas: the dt read is only started here, and workgroup 0's head,
+  // which needs P.dt, runs after the staging barrier)
+  unsigned long long dtb = 0;
+  if (SG) dtb = dt_tile_issue(P, sc, slot);
+  else apply_dt(P, sc, slot, true);
+  if (!SG && b == 0) lean_tile_wg0_head<OUT && !RES && !FX, FX>(P, sc, slot, slot_next, X, seq_prev);
   int i[CPT], j[CPT], c[CPT], i0, j0;
   bool mine[CPT];
   // own-cell global inputs first, so they are in flight during the staging
@@ -139,11 +213,46 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
 #pragma unroll
   for (int q = 0; q < CPT; q++) {
     mine[q] = lean_tile_cell(P, T, (int)b, (int)threadIdx.x, &i[q], &j[q], &c[q], &i0, &j0, q);
-    if (mine[q]) lean_load_own<TileIO<SG>::NE>(L, (long)i[q] * P.ny + j[q], own[q]);
+    if (mine[q]) {
+      if (SG) lean_load_own_flags(L, (long)i[q] * P.ny + j[q], own[q]);
+      else lean_load_own<TileIO<SG>::NE>(L, (long)i[q] * P.ny + j[q], own[q]);
+    }
   }
-  if (!FX || seq_prev == 0 || (X.skip & 4) || (i0 - 1 > P.i0 - 1 && i0 + T.TI < P.i1)) {
+  // staged from the state arrays alone (not an edge tile of a fused exchange)
+  const bool plain = !FX || seq_prev == 0 || (X.skip & 4) || (i0 - 1 > P.i0 - 1 && i0 + T.TI < P.i1);
+  if (SG && plain) {
+    // Ordered so that a wave's independent loads overlap: the dt word and
+    // the own cells' CT / lb are in flight; the whole staging is issued next,
+    // then -- the only wait in front of them is the one for CT -- the own
+    // cells' beta / CP / R / kk; dt is finished while those travel, and the
+    // LDS stores come last.  (Common code between the two K dispatches, not
+    // a copy per K: the compiler hoists the CT test out of per-K copies to
+    // in front of the staging loads.)
+    constexpr int KMAX = lean_stage_kmax(NT, CPT);
+    static_assert(KMAX <= LEAN_STAGE_KTOP, "lean_tile_body dispatches K <= LEAN_STAGE_KTOP");
+    LeanStaged<KMAX> s;
+    const int K = T.stage;   // (beyond KMAX the host sends 0)
+    if (KMAX >= 2 && K == 2) lean_stage_issue<(KMAX >= 2 ? 2 : 0), NT>(P, L, T, i0, j0, s);
+    else if (KMAX >= 3 && K == 3) lean_stage_issue<(KMAX >= 3 ? 3 : 0), NT>(P, L, T, i0, j0, s);
+#pragma unroll
+    for (int q = 0; q < CPT; q++) {
+      // (the Euler step tests bits of CT's low word only)
+      keep_whole(own[q].CT);
+      if (mine[q]) lean_load_own_rest<4>(L, (long)i[q] * P.ny + j[q], own[q]);
+    }
+    dt_tile_finish(P, dtb);
+    if (KMAX >= 2 && K == 2) lean_stage_write<(KMAX >= 2 ? 2 : 0)>(T, s, lds);
+    else if (KMAX >= 3 && K == 3) lean_stage_write<(KMAX >= 3 ? 3 : 0)>(T, s, lds);
+    else lean_tile_stage<true>(P, L, T, i0, j0, lds, threadIdx.x, NT);
+  } else if (plain) {
     lean_tile_stage<SG>(P, L, T, i0, j0, lds, threadIdx.x, NT);
   } else {
+    if (SG) {
+#pragma unroll
+      for (int q = 0; q < CPT; q++)
+        if (mine[q]) lean_load_own_rest<4>(L, (long)i[q] * P.ny + j[q], own[q]);
+      dt_tile_finish(P, dtb);
+    }
     // edge tile: the ghost column comes from the mailbox of parity seq_prev
     constexpr int NF = SG ? LEAN_TILE_FIELDS_SG : LEAN_TILE_FIELDS;
     const int pp = (int)(seq_prev & 1);
@@ -176,6 +285,7 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
     }
   }
   __syncthreads();
+  if (SG && b == 0) lean_tile_wg0_head<OUT && !RES && !FX, FX>(P, sc, slot, slot_next, X, seq_prev);
   // (raising the wave priority here for the compute phase, s_setprio 2,
   // measured no change: headline 26.9 - 27.2 us either way, triple point
   // 350 - 353 us)

@@ -113,7 +113,17 @@ inline TileTrK tile_tr_kernel(int nt, bool sg, int cpt) {
   return nt == BLOCK ? kTileTr[sg][cpt - 1] : kTileTrNt[nt == 128 ? 0 : 1][cpt - 1];
 }
 
-using LeanEulerK = void (*)(StepParams, LeanSoA, long, long, DevScalars*, int, int, int, ResidualPack*);
+// slots per thread of the batched staging for tile T (single gas), 0 where
+// the kernel of nt threads and cpt cells per thread stages with the loop
+inline int tile_stage_k(const LeanTile& T, int nt, int cpt) {
+  const int K = (T.NC + nt - 1) / nt;
+  return K <= lean_stage_kmax(nt, cpt) ? K : 0;
+}
+int lean_tile_stage_kmax(int nt, int cpt) {
+  return (nt == BLOCK || nt == 128 || nt == 64) && (cpt == 1 || cpt == 2) ? lean_stage_kmax(nt, cpt) : 0;
+}
+
+using LeanEulerK =void (*)(StepParams, LeanSoA, long, long, DevScalars*, int, int, int, ResidualPack*);
 // [residual][first lean step: from the generic arrays]
 static const LeanEulerK kLeanEuler[2][2] = {{hf2d_lean_euler<false, false>, hf2d_lean_euler<false, true>},
                                             {hf2d_lean_euler<true, false>, hf2d_lean_euler<true, true>}};
@@ -153,7 +163,8 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
     const LeanTile T2 = lean_tile_geom(P.i1 - P.i0, P.ny, BLOCK, lean_tj, 2);
     if ((long)T2.nbi * T2.nbj < 2L * cu_count) cpt = 1;
   }
-  const LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, nt, lean_tj, cpt);
+  LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, nt, lean_tj, cpt);
+  T.stage = sg ? tile_stage_k(T, nt, cpt) : 0;
   const unsigned ntile = (unsigned)(T.nbi * T.nbj);
   size_t shmem = (size_t)lean_tile_fields(sg) * T.NC * sizeof(real);
   if (lean_wgcu > 0)   // cap the resident workgroups per CU through the LDS request (160 KB per CU)
@@ -185,6 +196,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
   lean_tile_last.TJ = T.TJ;
   lean_tile_last.nbi = T.nbi;
   lean_tile_last.nbj = T.nbj;
+  lean_tile_last.stage = T.stage;
   // (the stagger block is compiled into the single-gas two-cell 256-thread plain kernel only)
   lean_tile_last.stagger = HF2D_TILE_STAGGER && sg && cpt == 2 && !fx_step && nt == BLOCK ? P.stagger : 0;
   lean_tile_last.fx = fx_step ? 1 : 0;
