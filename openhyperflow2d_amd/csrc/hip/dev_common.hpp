@@ -108,9 +108,10 @@ __device__ inline double dt_cur_tile(const StepParams& P, const DevScalars* sc, 
   if (P.dt_read == 1) return dt_get_wave(sc, slot);
   return dt_get(sc, slot);
 }
-// first kernel of a lagged step, one thread, before the slot's word is
-// overwritten with this step's dt: the previous step's MIN goes to the next
-// step's lag word (fold: the MIN over the other ranks, if it is still pending)
+// first kernel of a lagged step, one thread (step_head), before the slot's
+// word is overwritten with this step's dt: the previous step's MIN goes to the
+// next step's lag word (fold: the MIN over the other ranks, if it is still
+// pending)
 __device__ inline void lag_head(const StepParams& P, DevScalars* sc, int slot, int slot_next, double fold = 1.0) {
   if (P.lag_dt) {
     const double m = dt_get(sc, slot);
@@ -162,9 +163,8 @@ __device__ inline void dt_tile_finish(StepParams& P, unsigned long long b) {
   P.dtdy = dt / P.dy;
 }
 
-// Run once per step by one thread of the step's first kernel: iteration
-// number and CFL / beta scenario values (SolverBase::make_params arithmetic)
-// of the next step.
+// Once per step (step_head): iteration number and CFL / beta scenario values
+// (SolverBase::make_params arithmetic) of the next step.
 __device__ inline void scenario_next(const StepParams& P, DevScalars* sc, int slot, int slot_next) {
   const double it = sc->iter[slot] + 1.0;
   sc->iter[slot_next] = it;
@@ -202,6 +202,73 @@ __device__ inline void shfl_merge(ResidualPack& r, int off) {
     f.sum_div += o.sum_div;
     f.count += o.count;
   }
+}
+
+// A thread's residual before its cell, and the wave's merged pack into slot
+// b * (NT / WAVE) + wave of the partials, by lane 0 (every lane active).
+// Sites that write these and the helpers below out instead, because a kernel's
+// registers or spills move with the call: profiles/step_epilogue_ab.md.
+__device__ __forceinline__ void residual_begin(ResidualPack& r) {
+  residual_reset(r);
+#pragma unroll
+  for (int k = 0; k < NEQ; k++) r.eq[k].i = r.eq[k].j = -1;
+}
+template <int NT>
+__device__ __forceinline__ void residual_publish(ResidualPack& r, ResidualPack* partials, unsigned b) {
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
+  if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)b * (NT / WAVE) + threadIdx.x / WAVE] = r;
+}
+
+// Once per step, by one thread of the step's first kernel (the caller tests
+// for it), dt being the step's: resets the slot the NEXT step accumulates into
+// (never the one this step min-reduces into, which other workgroups may
+// already be writing), moves the lagged dt on, accumulates physical time and
+// sets the next step's iteration and scenario values.  A kernel's own words
+// (dt_val, hot_cnt, the host mirror) follow the call.  The three tile steps'
+// heads keep the five lines written out: a change here goes there too.
+__device__ __forceinline__ void step_head(const StepParams& P, DevScalars* sc, int slot, int slot_next, double dt,
+                                          double fold = 1.0) {
+  dt_reset(sc, slot_reset(slot));
+  lag_head(P, sc, slot, slot_next, fold);
+  sc->dt_bits[slot] = d_to_bits(dt);   // folded (later kernels of the step read the word)
+  sc->time_part += dt;
+  scenario_next(P, sc, slot, slot_next);
+}
+
+// MIN of a workgroup's dt limits into the slot the next step reads, around the
+// caller's __syncthreads(): block_dt_stage, every thread: the wave's MIN into
+// the workgroup's LDS words (returned); block_dt_commit, thread 0 after the
+// barrier: their MIN into the slot's shard.  serial: the reference's serial
+// build keeps dt a running minimum, so the step's dt joins in.  have_slot
+// false sends nothing (the lean N-S materialize's fill: slot_next < 0);
+// skip_unset sends nothing while the MIN is the initial 1.0 (hf2d_lnm_hot: a
+// workgroup without a listed cell).  dtl and dt keep the caller's type, so the
+// FP32 build converts where the written-out code did.
+constexpr bool DT_HAVE_SLOT = true, DT_SKIP_UNSET = true;   // the guards, for a call that names them
+template <int NT, class T>
+__device__ __forceinline__ double* block_dt_stage(T dtl) {
+  __shared__ double sdt[NT / WAVE];
+  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
+  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
+  return sdt;
+}
+template <int NT, class T>
+__device__ __forceinline__ void block_dt_commit(const double* sdt, DevScalars* sc, int slot_next, int serial, T dt,
+                                                bool have_slot = true, bool skip_unset = false) {
+  double m = sdt[0];
+  for (int q = 1; q < NT / WAVE; q++) m = fmin(m, sdt[q]);
+  if (serial) m = fmin(m, dt);
+  if (have_slot && (!skip_unset || m < 1.0)) dt_min(sc, slot_next, m);
+}
+
+// Cell (i, j) of the flat x-major index c of the one-cell-per-thread kernels.
+struct CellIJ {
+  int i, j;
+};
+__device__ __forceinline__ CellIJ cell_ij(long c, int ny) {
+  const int i = (int)(c / ny);
+  return {i, (int)(c - (long)i * ny)};
 }
 
 // Workgroups are dispatched round-robin over the 8 XCDs (each with its own

@@ -223,6 +223,13 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   int dev = 0;
   int gi0 = 0, gi1 = 0, l_off = 0;
   int abuf = 0, dsbuf = 0, pbuf = 0, sbuf = 0;  // ping-pong indices (sbuf: current state)
+  // a lean step's output arrays become the state (the split and fused Euler
+  // steps flip other subsets and write theirs out)
+  void flip_state() {
+    sbuf = 1 - sbuf;
+    dsbuf = 1 - dsbuf;
+    pbuf = 1 - pbuf;
+  }
   int cbuf = 0;           // lean N-S: CP/mu/lam/k level ping-pong (0: the generic arrays)
   int lean_state = 0;     // 1: lean arrays authoritative (A/B/F/p stale)
   int lns_state = 0;      // 1: lean N-S buffers authoritative (committed S, A/B/F, p stale); shared with the lean mechanism path

@@ -291,11 +291,7 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
   // 350 - 353 us)
   if (TR) tr[1] = rt_clock();
   ResidualPack r;
-  if (RES) {
-    residual_reset(r);
-#pragma unroll
-    for (int k = 0; k < NEQ; k++) r.eq[k].i = r.eq[k].j = -1;
-  }
+  if (RES) residual_begin(r);
   double dtl = 1.0;
   int neg = 0;
 #pragma unroll
@@ -328,14 +324,8 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
     }
   }
   if (TR) tr[2] = rt_clock();
-  if (RES) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)b * (NT / WAVE) + threadIdx.x / WAVE] = r;
-  }
-  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
-  __shared__ double sdt[NT / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
+  if (RES) residual_publish<NT>(r, partials, b);
+  const double* sdt = block_dt_stage<NT>(dtl);
   if (neg) {
     atomicOr(&sc->neg_T, 1);
     if (OUT && !RES && !FX && P.host_sc) vm_drain();   // (done before host_mirror_tail's count)
@@ -343,10 +333,7 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
   __syncthreads();
   if (TR) tr[3] = rt_clock();
   if (threadIdx.x == 0) {
-    double m = sdt[0];
-    for (int q = 1; q < NT / WAVE; q++) m = fmin(m, sdt[q]);
-    if (serial) m = fmin(m, P.dt);
-    dt_min(sc, slot_next, m);
+    block_dt_commit<NT>(sdt, sc, slot_next, serial, P.dt);
     if (TR) {
       vm_drain();
       tr[4] = rt_clock();

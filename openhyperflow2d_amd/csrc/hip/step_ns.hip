@@ -32,16 +32,9 @@ __global__ __launch_bounds__(BLOCK) void hf2d_predict(StepParams P, SoA in, SoA 
   const unsigned blk = split_block(P);
   const long g = (long)blk * BLOCK + threadIdx.x;
   if (g == 0) {
-    // Reset the slot the NEXT step will accumulate into (never the one this
-    // step's fill is min-reducing, which other blocks may already be
-    // writing) and accumulate physical time.
-    dt_reset(sc, slot_reset(slot));
-    lag_head(P, sc, slot, slot_next);
-    sc->dt_bits[slot] = d_to_bits(P.dt);   // folded (later kernels of the step read the word)
-    sc->time_part += P.dt;
+    step_head(P, sc, slot, slot_next, P.dt);
     sc->dt_val[slot] = P.dt;
     sc->hot_cnt[slot_next] = 0;
-    scenario_next(P, sc, slot, slot_next);
   }
   const long c = c0 + g;
   ResidualPack r;
@@ -51,14 +44,10 @@ __global__ __launch_bounds__(BLOCK) void hf2d_predict(StepParams P, SoA in, SoA 
     for (int k = 0; k < NEQ; k++) r.eq[k].i = r.eq[k].j = -1;
   }
   if (c < c1) {
-    const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+    const auto [i, j] = cell_ij(c, P.ny);
     predict_cell_t<RES, MODE>(P, in, out, i, j, r);
   }
-  if (RES) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)blk * (BLOCK / WAVE) + threadIdx.x / WAVE] = r;
-  }
+  if (RES) residual_publish<BLOCK>(r, partials, blk);
 }
 
 template <int MODE, int NSB, bool LAZY = false>
@@ -91,20 +80,14 @@ __device__ __forceinline__ void fill_body(StepParams& P, const SoA& sin, const S
   double dtl = 1.0;
   int neg = 0;
   if (c < c1) {
-    const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+    const auto [i, j] = cell_ij(c, P.ny);
     dtl = fill_cell<MODE, NSB, LAZY>(P, sin, pold, out, i, j, &neg, store_grad != 0);
   }
-  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
-  __shared__ double sdt[BLOCK / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
+  const double* sdt = block_dt_stage<BLOCK>(dtl);
   if (neg) atomicOr(&sc->neg_T, 1);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = sdt[0];
-    for (int q = 1; q < BLOCK / WAVE; q++) m = fmin(m, sdt[q]);
-    if (serial) m = fmin(m, P.dt);  // serial build: dt is a running minimum
-    if (slot_next >= 0) dt_min(sc, slot_next, m);   // < 0: lean N-S materialize
-  }
+  // (slot_next < 0: lean N-S materialize)
+  if (threadIdx.x == 0) block_dt_commit<BLOCK>(sdt, sc, slot_next, serial, P.dt, slot_next >= 0);
 }
 
 // Mechanism mode, operator-split kinetics (runtime mechanism data; the
@@ -116,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void hf2d_chem_generic(StepParams P, SoA mid
   apply_dt(P, sc, slot);
   const long c = c0 + (long)blockIdx.x * BLOCK + threadIdx.x;
   if (c < c1) {
-    const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+    const auto [i, j] = cell_ij(c, P.ny);
     mech_chem_soa_cell<NSB>(P, mid, out, Tprev, i, j);
   }
 }
@@ -130,13 +113,7 @@ __global__ __launch_bounds__(BLOCK) void hf2d_fused_euler(StepParams P, SoA in, 
                                                            ResidualPack* partials) {
   apply_dt(P, sc, slot);
   const long g = (long)blockIdx.x * BLOCK + threadIdx.x;
-  if (g == 0) {
-    dt_reset(sc, slot_reset(slot));
-    lag_head(P, sc, slot, slot_next);
-    sc->dt_bits[slot] = d_to_bits(P.dt);   // folded (later kernels of the step read the word)
-    sc->time_part += P.dt;
-    scenario_next(P, sc, slot, slot_next);
-  }
+  if (g == 0) step_head(P, sc, slot, slot_next, P.dt);
   const long c = c0 + g;
   ResidualPack r;
   if (RES) {
@@ -147,20 +124,18 @@ __global__ __launch_bounds__(BLOCK) void hf2d_fused_euler(StepParams P, SoA in, 
   double dtl = 1.0;
   int neg = 0;
   if (c < c1) {
-    const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+    const auto [i, j] = cell_ij(c, P.ny);
     predict_cell_t<RES>(P, in, mid, i, j, r);
     dtl = fill_cell(P, mid, mid, out, i, j, &neg, false);
   }
-  if (RES) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE] = r;
-  }
+  if (RES) residual_publish<BLOCK>(r, partials, blockIdx.x);
   for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
   __shared__ double sdt[BLOCK / WAVE];
   if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
   if (neg) atomicOr(&sc->neg_T, 1);
   __syncthreads();
+  // (block_dt_stage / block_dt_commit written out, with a test that is dead here -- the one launch
+  // passes (nstep + 1) % 3: either change moves this kernel's spills, profiles/step_epilogue_ab.md)
   if (threadIdx.x == 0) {
     double m = sdt[0];
     for (int q = 1; q < BLOCK / WAVE; q++) m = fmin(m, sdt[q]);
@@ -172,7 +147,7 @@ __global__ __launch_bounds__(BLOCK) void hf2d_fused_euler(StepParams P, SoA in, 
 __global__ __launch_bounds__(BLOCK) void hf2d_wall_solid(StepParams P, SoA s, real* qdir, long c0, long c1) {
   const long c = c0 + (long)blockIdx.x * BLOCK + threadIdx.x;
   if (c >= c1) return;
-  const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+  const auto [i, j] = cell_ij(c, P.ny);
   wall_heat_solid_cell(P, s, qdir, i, j);
 }
 
@@ -181,7 +156,7 @@ __global__ __launch_bounds__(BLOCK) void hf2d_wall_wall(StepParams P, SoA s, con
   apply_dt(P, sc, slot);
   const long c = c0 + (long)blockIdx.x * BLOCK + threadIdx.x;
   if (c >= c1) return;
-  const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+  const auto [i, j] = cell_ij(c, P.ny);
   wall_heat_wall_cell(P, s, qdir, i, j);
 }
 
@@ -687,23 +662,12 @@ __device__ __forceinline__ void lns_step_body(StepParams& P, const LnsArrays& a,
                                                          &f2);
     }
   }
-  if (RES) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)b * (BLOCK / WAVE) + threadIdx.x / WAVE] = r;
-  }
-  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
-  __shared__ double sdt[BLOCK / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
+  if (RES) residual_publish<BLOCK>(r, partials, b);
+  const double* sdt = block_dt_stage<BLOCK>(dtl);
   if (neg) atomicOr(&sc->neg_T, 1);
   if (skip) atomicOr(&sc->neg_T, LNS_SKIP_ERR);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = sdt[0];
-    for (int q = 1; q < BLOCK / WAVE; q++) m = fmin(m, sdt[q]);
-    if (serial) m = fmin(m, P.dt);
-    dt_min(sc, slot_next, m);
-  }
+  if (threadIdx.x == 0) block_dt_commit<BLOCK>(sdt, sc, slot_next, serial, P.dt);
   if (FX && !(X.skip & 2)) fx_edge_push(P, X, Lc, T, i0, j0, seq_prev);
   // (unpacking the peers' halo in this last workgroup instead of a separate
   // hf2d_p2p_unpack launch measured 2x the exchange cost: one workgroup's
@@ -848,10 +812,8 @@ DeviceSolver::StepDone DeviceSolver::step_lean_ns(const StepCtx& c) {
                        m.partials, 0);
   }
   HIP_CHECK(hipGetLastError());
-  sbuf = 1 - sbuf;
-  pbuf = 1 - pbuf;
+  flip_state();
   cbuf = 1 - cbuf;
-  dsbuf = 1 - dsbuf;
   lns_steps++;
   if (lns_split) {
     HIP_CHECK(hipEventRecord(m.ev_edge, st));
@@ -1154,6 +1116,7 @@ __device__ __forceinline__ void lnm_step_body(StepParams& P, const LnmArrays& a,
   }
   if (tr0) tr[6] = rt_clock();
   if (trl) tr[10] = rt_clock();
+  // (residual_publish and the dt reduction written out: profiles/step_epilogue_ab.md)
   if (RES) {
 #pragma unroll
     for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
@@ -1213,18 +1176,12 @@ __global__ __launch_bounds__(BLOCK) void hf2d_lnm_hot(StepParams P, LnmArrays a,
     a.CPso[idx] = st.CP;
     a.kso[idx] = st.k;
   }
-  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
-  __shared__ double sdt[BLOCK / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
+  const double* sdt = block_dt_stage<BLOCK>(dtl);
   if (neg) atomicOr(&sc->neg_T, 1);
   if (skip) atomicOr(&sc->neg_T, LNS_SKIP_ERR);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double mn = sdt[0];
-    for (int q = 1; q < BLOCK / WAVE; q++) mn = fmin(mn, sdt[q]);
-    if (serial) mn = fmin(mn, P.dt);
-    if (mn < 1.0) dt_min(sc, slot_next, mn);
-  }
+  // (a workgroup without a listed cell sends nothing)
+  if (threadIdx.x == 0) block_dt_commit<BLOCK>(sdt, sc, slot_next, serial, P.dt, DT_HAVE_SLOT, DT_SKIP_UNSET);
 }
 
 // The lean mechanism step applies (lean_mech.hpp; eligibility lnm_ok) with a
@@ -1350,10 +1307,8 @@ DeviceSolver::StepDone DeviceSolver::lnm_step(const StepCtx& c) {
       overlap_steps++;
     }
   }
-  sbuf = 1 - sbuf;
-  pbuf = 1 - pbuf;
+  flip_state();
   cbuf = 1 - cbuf;
-  dsbuf = 1 - dsbuf;
   lnm_steps++;
   // the new state's halo (post-step buffers), overlapped with the interior
   if (lnm_split && !m.p2p.on) overlap_exchange(CpuSolver::HALO_LNS, slot_next);

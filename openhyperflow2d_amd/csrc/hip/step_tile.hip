@@ -14,48 +14,27 @@ __global__ __launch_bounds__(BLOCK) void hf2d_lean_euler(StepParams P, LeanSoA L
   apply_dt(P, sc, slot);
   const unsigned b = xcd_remap(blockIdx.x, gridDim.x);
   const long g = (long)b * BLOCK + threadIdx.x;
-  if (g == 0) {
-    dt_reset(sc, slot_reset(slot));
-    lag_head(P, sc, slot, slot_next);
-    sc->dt_bits[slot] = d_to_bits(P.dt);   // folded (later kernels of the step read the word)
-    sc->time_part += P.dt;
-    scenario_next(P, sc, slot, slot_next);
-  }
+  if (g == 0) step_head(P, sc, slot, slot_next, P.dt);
   const long c = c0 + g;
   ResidualPack r;
-  if (RES) {
-    residual_reset(r);
-#pragma unroll
-    for (int k = 0; k < NEQ; k++) r.eq[k].i = r.eq[k].j = -1;
-  }
+  if (RES) residual_begin(r);
   double dtl = 1.0;
   int neg = 0;
   if (c < c1) {
-    const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+    const auto [i, j] = cell_ij(c, P.ny);
     dtl = lean_euler_cell<RES, FROMG>(P, L, i, j, r, &neg);
   }
-  if (RES) {
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) shfl_merge(r, off);
-    if ((threadIdx.x & (WAVE - 1)) == 0) partials[(long)b * (BLOCK / WAVE) + threadIdx.x / WAVE] = r;
-  }
-  for (int off = 1; off < WAVE; off <<= 1) dtl = fmin(dtl, __shfl_xor(dtl, off, WAVE));
-  __shared__ double sdt[BLOCK / WAVE];
-  if ((threadIdx.x & (WAVE - 1)) == 0) sdt[threadIdx.x / WAVE] = dtl;
+  if (RES) residual_publish<BLOCK>(r, partials, b);
+  const double* sdt = block_dt_stage<BLOCK>(dtl);
   if (neg) atomicOr(&sc->neg_T, 1);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double m = sdt[0];
-    for (int q = 1; q < BLOCK / WAVE; q++) m = fmin(m, sdt[q]);
-    if (serial) m = fmin(m, P.dt);
-    dt_min(sc, slot_next, m);
-  }
+  if (threadIdx.x == 0) block_dt_commit<BLOCK>(sdt, sc, slot_next, serial, P.dt);
 }
 
 __global__ __launch_bounds__(BLOCK) void hf2d_lean_materialize(StepParams P, LeanSoA L, SoA g, long c0, long c1) {
   const long c = c0 + (long)blockIdx.x * BLOCK + threadIdx.x;
   if (c >= c1) return;
-  const int i = (int)(c / P.ny), j = (int)(c - (long)i * P.ny);
+  const auto [i, j] = cell_ij(c, P.ny);
   lean_materialize_cell(P, L, g, i, j);
 }
 
@@ -217,9 +196,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
     hipLaunchKernelGGL(pk, dim3(ne), dim3(nt), shmem, st, P, L, T, m.sc, slot, slot_next, serial, m.partials,
                        parts ? 1 : 0);
     HIP_CHECK(hipGetLastError());
-    sbuf = 1 - sbuf;   // the new state is this step's output arrays
-    dsbuf = 1 - dsbuf;
-    pbuf = 1 - pbuf;
+    flip_state();   // the new state is this step's output arrays
     HIP_CHECK(hipEventRecord(m.ev_edge, st));
     // interior tiles in flight before the (possibly host-blocking) exchange
     // is issued; they write neither the edge columns nor the ghost columns
@@ -274,9 +251,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
     dt_word_valid = fold;
   }
   HIP_CHECK(hipGetLastError());
-  sbuf = 1 - sbuf;
-  dsbuf = 1 - dsbuf;
-  pbuf = 1 - pbuf;
+  flip_state();
   return {ntile, nt / WAVE, fx_step};
 }
 
@@ -288,9 +263,7 @@ DeviceSolver::StepDone DeviceSolver::step_lean_flat(const StepCtx& c) {
   hipLaunchKernelGGL(kLeanEuler[c.want_res][fromg], dim3(c.nblk), dim3(BLOCK), 0, m.stream, c.P, L, c.c0, c.c1, m.sc,
                      c.slot, c.slot_next, c.serial, m.partials);
   HIP_CHECK(hipGetLastError());
-  sbuf = 1 - sbuf;
-  dsbuf = 1 - dsbuf;
-  pbuf = 1 - pbuf;
+  flip_state();
   lean_state = 1;
   lean_T_stored = true;   // (the flat kernel always writes the output-only fields)
   return {c.nblk, BLOCK / WAVE, false};

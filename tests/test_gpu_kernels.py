@@ -1081,3 +1081,65 @@ def test_wall_blend_gpu_equals_cpu(gpu):
     for f in FIELDS + ["mu_t"]:
         np.testing.assert_array_equal(g.field(f), c.field(f), err_msg=f)
     assert not np.array_equal(g.field("U"), r.field("U"))
+
+
+SERIAL_CALLS = [(1, False), (3, True), (7, False), (1, True)]
+_serial_cpu_cache = {}
+
+
+def _serial_deck(ns):
+    return decks.wedge15(80, 30, navier_stokes=ns, nmax=10 ** 6, nout=10 ** 5)
+
+
+def _serial_cpu(hf, ns):
+    """CPU stepper over SERIAL_CALLS, once per deck: (dt, time) after every
+    call under both semantics, and the final fields under "serial"."""
+    if ns not in _serial_cpu_cache:
+        out, sims = {}, {}
+        for sem in ("mpi", "serial"):
+            c = sims[sem] = hf.Simulation(_serial_deck(ns), "cpu", semantics=sem)
+            seq = []
+            for n, res in SERIAL_CALLS:
+                c.step(n, residual=res)
+                s = c.summary()
+                seq.append((s["dt"], s["time"]))
+            out[sem] = seq
+        out["fields"] = {f: sims["serial"].field(f).copy() for f in FIELDS}
+        _serial_cpu_cache[ns] = out
+    return _serial_cpu_cache[ns]
+
+
+@pytest.mark.parametrize("path", ["lean", "fused", "ns_fill"])
+def test_serial_semantics_gpu_equals_cpu(gpu, path):
+    """semantics="serial" (dt is the running minimum of the reference's serial
+    build: every workgroup's dt MIN takes the step's own dt in) on the three
+    step ends that read the flag differently: the flat first lean step and
+    then the tile kernel, hf2d_fused_euler, and the split fill of a laminar
+    N-S deck.  dt and time after every call equal the CPU's (Euler: bit for
+    bit), dt never rises, and the fields agree at the end.  The deck tells the
+    two semantics apart within these 12 steps: the CPU's dt sequences differ."""
+    ns = path == "ns_fill"
+    ref = _serial_cpu(gpu, ns)
+    assert [d for d, _ in ref["mpi"]] != [d for d, _ in ref["serial"]]
+    g = gpu.Simulation(_serial_deck(ns), "gpu", semantics="serial", lean=path != "fused")
+    if ns:
+        g.solver.lean_ns = False
+    elif path == "lean":
+        assert g.solver.lean_ok, g.solver.lean_why
+    prev = None
+    for (n, res), (dt_c, t_c) in zip(SERIAL_CALLS, ref["serial"]):
+        g.step(n, residual=res)
+        s = g.summary()
+        if ns:
+            assert abs(s["dt"] - dt_c) <= 1e-12 * dt_c
+            assert abs(s["time"] - t_c) <= 1e-10 * t_c
+        else:
+            assert s["dt"] == dt_c and s["time"] == t_c
+        assert prev is None or s["dt"] <= prev
+        prev = s["dt"]
+        if path == "lean" and n > 1:   # (the first lean step is the flat kernel)
+            assert g.solver.lean_tile_last["nt"] > 0
+    if ns:
+        assert g.solver.lns_steps == 0
+    for f in FIELDS:
+        assert _rel(g.field(f), ref["fields"][f]) < (1e-9 if ns else 1e-11), f
