@@ -6,6 +6,7 @@
                                      [--profile FILE] [--fault-inject step:N,rank:R,kind:nan|kill]
                                      [--transport p2p|rccl]
                                      [--probe-history FILE.npz [--probe-capacity N]]
+                                     [--load-history FILE.npz [--load-capacity N]]
                                      [--averages FILE.npz [--averages-every K] [--averages-favre]
                                       [--averages-species all|A,B,...]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
@@ -46,6 +47,11 @@ def _cmd_run(a) -> int:
             print("--probe-history records in one process only; this is a %d-rank launch "
                   "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
         return 2
+    if a.load_history and world > 1:
+        if rank == 0:
+            print("--load-history records in one process only; this is a %d-rank launch "
+                  "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
+        return 2
     if a.averages and world > 1:
         if rank == 0:
             print("--averages accumulates in one process only; this is a %d-rank launch "
@@ -84,6 +90,16 @@ def _cmd_run(a) -> int:
         except (ValueError, RuntimeError) as e:
             print("--probe-history: %s" % e, file=sys.stderr, flush=True)
             return 2
+    load_boxes, load_cuts = [], []
+    if a.load_history:
+        # what the driver integrates once per cycle, every step: the body box
+        # (is_Cx_calc), the X cuts and the nozzle cut (is_Cd_calc)
+        load_boxes, load_cuts = (list(v) for v in sim.case.load_targets)
+        try:
+            sim.record_loads(load_boxes, load_cuts, a.load_capacity)
+        except (ValueError, RuntimeError) as e:
+            print("--load-history: %s" % e, file=sys.stderr, flush=True)
+            return 2
     if a.averages:
         try:
             sp = a.averages_species
@@ -111,6 +127,20 @@ def _cmd_run(a) -> int:
                      vars=np.asarray(PROBE_VARS), total=np.int64(h["total"]))
         print("probe history: %d of %d steps x %d points -> %s" % (h["values"].shape[0], h["total"], len(probe_cells),
                                                                     a.probe_history), flush=True)
+    if a.load_history:
+        import numpy as np
+
+        from .models.simulation import LOAD_PARTS
+
+        h = sim.load_history()
+        with open(a.load_history, "wb") as f:   # (np.savez on a path would append ".npz")
+            np.savez(f, times=h["times"], forces=h["forces"], mass_flow=h["mass_flow"],
+                     box_terms=h["terms"]["box_terms"], cut_terms=h["terms"]["cut_terms"], span=h["span"],
+                     total=np.int64(h["total"]), boxes=np.asarray(load_boxes, dtype=np.float64).reshape(-1, 4),
+                     cuts=np.asarray(load_cuts, dtype=np.float64).reshape(-1, 3), parts=np.asarray(LOAD_PARTS))
+        print("load history: %d of %d steps x %d boxes, %d cuts -> %s" % (h["times"].shape[0], h["total"],
+                                                                           len(load_boxes), len(load_cuts),
+                                                                           a.load_history), flush=True)
     if a.averages:
         import numpy as np
 
@@ -218,6 +248,12 @@ def main(argv=None) -> int:
                         "and write times / values / cells / vars to this file")
     r.add_argument("--probe-capacity", dest="probe_capacity", type=int, default=4096, metavar="N",
                    help="rows the recorder keeps: the last N steps (default 4096)")
+    r.add_argument("--load-history", dest="load_history", metavar="FILE.npz",
+                   help="record the body force parts of the deck's body box (is_Cx_calc) and the mass flow through "
+                        "its X cuts and the nozzle cut after every step (one process only) and write times / forces / "
+                        "mass_flow / box_terms / cut_terms / span / total / boxes / cuts / parts to this file")
+    r.add_argument("--load-capacity", dest="load_capacity", type=int, default=4096, metavar="N",
+                   help="rows the load recorder keeps: the last N steps (default 4096)")
     r.add_argument("--averages", metavar="FILE.npz",
                    help="accumulate time-averaged p, T, rho, U, V, their variances and the U-V covariance over the "
                         "whole field at every step (one process only) and write mean / var / cov_uv / vars / time / "

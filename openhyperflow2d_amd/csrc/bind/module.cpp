@@ -313,6 +313,16 @@ PYBIND11_MODULE(_hf2d, m) {
                                  v.emplace_back((int)(m.x / c.cfg.dx), (int)(m.y / c.cfg.dy));
                                return v;
                              })
+      .def_property_readonly("load_targets",
+                             [](const Case& c) {   // what the driver integrates: (boxes, cuts) for record_loads
+                               const Config& C = c.cfg;
+                               std::vector<LoadBox> boxes;
+                               std::vector<LoadCut> cuts;
+                               if (C.is_Cx_calc) boxes.push_back({C.x0_body, C.y0_body, C.dx_body, C.dy_body});
+                               for (const XCut& x : C.xcuts) cuts.push_back({(double)x.x0, (double)x.y0, (double)x.dy});
+                               if (C.is_Cd_calc) cuts.push_back({C.x0_nozzle, C.y0_nozzle, C.dy_nozzle});
+                               return py::make_tuple(boxes, cuts);
+                             })
       .def("set_min_distance_to_wall", &Case::set_min_distance_to_wall, py::arg("x0") = 0.0)
       .def("set_min_distance_to_wall_bruteforce", &Case::set_min_distance_to_wall_bruteforce, py::arg("x0") = 0.0)
       .def("set_semantics", [](Case& c, const std::string& s) {
@@ -489,6 +499,20 @@ PYBIND11_MODULE(_hf2d, m) {
         need_whole(c);
         return y_force(c, c.J, x0, y0, dx, dy);
       })
+      .def("force_parts",
+           [](const Case& c, double x0, double y0, double dx, double dy) {
+             // the pressure and friction folds of x_force / y_force, the wall span and the term counts
+             need_whole(c);
+             std::vector<real> xp, xd, yp, yd, sp;
+             x_force_terms(c, c.J, x0, y0, dx, dy, 0, c.J.nx, xp, xd);
+             y_force_terms(c, c.J, x0, y0, dx, dy, 0, c.J.nx, yp, yd);
+             wall_span_terms(c, c.J, x0, y0, dx, dy, 0, c.J.nx, sp);
+             return py::make_tuple(fold_terms(xp), fold_terms(xd), fold_terms(yp), fold_terms(yd), fold_terms(sp),
+                                   (long)xp.size(), (long)xd.size(), (long)yp.size(), (long)yd.size());
+           },
+           py::arg("x0"), py::arg("y0"), py::arg("dx"), py::arg("dy"),
+           "(Fx_p, Fx_d, Fy_p, Fy_d, span, n_xp, n_xd, n_yp, n_yd): the folds of x_force_terms / y_force_terms / "
+           "wall_span_terms and the number of terms of each force list")
       .def("x_force_ysym", [](const Case& c, double x0, double l, double d) {
         need_whole(c);
         return x_force_ysym(c, c.J, x0, l, d);
@@ -661,6 +685,42 @@ PYBIND11_MODULE(_hf2d, m) {
              return d;
            })
       .def("clear_probe_history", &SolverBase::clear_probe_history)
+      .def("record_loads", &SolverBase::record_loads, py::arg("boxes"), py::arg("cuts"), py::arg("capacity") = 4096,
+           "arm the per-step load recorder: the pressure and friction parts of x_force / y_force of every box "
+           "(x0, y0, dx, dy) and mass_flow_x of every cut (x0, y0, dy), and the time, after every step")
+      .def("load_history",
+           [](SolverBase& s) {
+             LoadHistory H;
+             {
+               py::gil_scoped_release rel;
+               H = s.load_history();
+             }
+             const py::ssize_t n = (py::ssize_t)H.times.size(), nb = H.nboxes, nc = H.ncuts;
+             py::array_t<double> t(std::vector<py::ssize_t>{n});
+             py::array_t<real> f(std::vector<py::ssize_t>{n, nb, (py::ssize_t)LOAD_PARTS});
+             py::array_t<real> mf(std::vector<py::ssize_t>{n, nc});
+             py::array_t<long> bt(std::vector<py::ssize_t>{nb, (py::ssize_t)LOAD_PARTS});
+             py::array_t<long> ct(std::vector<py::ssize_t>{nc});
+             py::array_t<real> sp(std::vector<py::ssize_t>{nb});
+             std::copy(H.times.begin(), H.times.end(), t.mutable_data());
+             std::copy(H.forces.begin(), H.forces.end(), f.mutable_data());
+             std::copy(H.mass_flow.begin(), H.mass_flow.end(), mf.mutable_data());
+             std::copy(H.box_terms.begin(), H.box_terms.end(), bt.mutable_data());
+             std::copy(H.cut_terms.begin(), H.cut_terms.end(), ct.mutable_data());
+             std::copy(H.span.begin(), H.span.end(), sp.mutable_data());
+             py::dict terms;
+             terms["box_terms"] = bt;
+             terms["cut_terms"] = ct;
+             py::dict d;
+             d["times"] = t;
+             d["forces"] = f;
+             d["mass_flow"] = mf;
+             d["terms"] = terms;
+             d["span"] = sp;
+             d["total"] = H.total;
+             return d;
+           })
+      .def("clear_load_history", &SolverBase::clear_load_history)
       .def("start_averaging", &SolverBase::start_averaging, py::arg("every") = 1, py::arg("second_moments") = true,
            py::arg("step_weight") = false, py::arg("favre") = false, py::arg("species") = std::vector<int>{},
            "arm the whole-field accumulator: weighted running mean (and variances, U-V covariance) of "

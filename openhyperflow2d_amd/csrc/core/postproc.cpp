@@ -138,8 +138,8 @@ real calc_area(const Case& cs, const Field& J, real x0, real y0, real dy) {
 
 real mass_flow_rate_x(const Case& cs, const Field& J, real x0, real y0, real dy) {
   const Config& C = cs.cfg;
-  const unsigned i = (unsigned)(x0 / C.dx);
-  const unsigned j0 = (unsigned)(y0 / C.dy), j1 = (unsigned)((y0 + dy) / C.dy);
+  const CutCells q = cut_cells(C, x0, y0, dy);
+  const unsigned i = q.i, j0 = q.j0, j1 = q.j1;
   real Mp = 0;
   if ((int)i >= J.nx) return 0;
   for (int j = (int)j0; j < (int)j1 && j < J.ny; j++) {
@@ -147,10 +147,6 @@ real mass_flow_rate_x(const Case& cs, const Field& J, real x0, real y0, real dy)
     if (!n.is(CT_SOLID)) Mp += (C.FT == FT_FLAT) ? C.dy * n.S[I_RHOU] : 2 * M_PI * C.dy * n.y * n.S[I_RHOU];
   }
   return Mp;
-}
-
-static bool in_box(const Config& C, int i, int j, real x0, real y0, real dx, real dy) {
-  return i >= (int)(x0 / C.dx) && i <= (int)((x0 + dx) / C.dx) && j >= (int)(y0 / C.dy) && j <= (int)((y0 + dy) / C.dy);
 }
 
 void x_force_terms(const Case& cs, const Field& J, real x0, real y0, real dx, real dy, int ib, int ie,

@@ -41,6 +41,18 @@ void fold_heat_flux_y(std::vector<real>& Q, const std::vector<real>& jq);
 void write_y_heat_flux(const std::string& path, const Config& C, const std::vector<real>& Q);
 
 // libOutCFD
+// cell (i, j) inside the box of a body integral, and the column and rows of
+// an x cut: the reference's integer truncations, shared with the per-step
+// load recorder's plan (load_plan.hpp)
+inline bool in_box(const Config& C, int i, int j, real x0, real y0, real dx, real dy) {
+  return i >= (int)(x0 / C.dx) && i <= (int)((x0 + dx) / C.dx) && j >= (int)(y0 / C.dy) && j <= (int)((y0 + dy) / C.dy);
+}
+struct CutCells {
+  unsigned i, j0, j1;   // column; rows [j0, j1)
+};
+inline CutCells cut_cells(const Config& C, real x0, real y0, real dy) {
+  return {(unsigned)(x0 / C.dx), (unsigned)(y0 / C.dy), (unsigned)((y0 + dy) / C.dy)};
+}
 real p_asterisk(const CellRecord& n);
 real T_asterisk(const CellRecord& n);
 real schlieren(const CellRecord& n);

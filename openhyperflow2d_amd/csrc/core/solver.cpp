@@ -451,6 +451,20 @@ void SolverBase::record_probes(const std::vector<std::pair<int, int>>&, long) {
 ProbeHistory SolverBase::probe_history() { throw std::runtime_error("this backend has no per-step probe recorder"); }
 void SolverBase::clear_probe_history() {}
 
+void SolverBase::check_record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts,
+                                    long capacity) const {
+  check_loads(boxes, cuts, capacity);
+  const auto own = owned_columns();
+  if (comm->size() > 1 || own.first != 0 || own.second != cs.J.nx || !cs.J.whole())
+    throw std::runtime_error("record_loads: this solver is one strip of several; the per-step load recorder needs a "
+                             "one-process run (the serial fold runs over the whole field)");
+}
+void SolverBase::record_loads(const std::vector<LoadBox>&, const std::vector<LoadCut>&, long) {
+  throw std::runtime_error("this backend has no per-step load recorder");
+}
+LoadHistory SolverBase::load_history() { throw std::runtime_error("this backend has no per-step load recorder"); }
+void SolverBase::clear_load_history() {}
+
 void SolverBase::start_averaging(int, bool, bool, bool, const std::vector<int>&) {
   throw std::runtime_error("this backend has no flow-statistics accumulator");
 }
@@ -848,6 +862,25 @@ void CpuSolver::record_probes(const std::vector<std::pair<int, int>>& cells, lon
 
 void CpuSolver::clear_probe_history() { probe_total = 0; }
 
+void CpuSolver::record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) {
+  check_record_loads(boxes, cuts, capacity);
+  load_plan = build_load_plan(cs, cs.J, boxes, cuts, l_off);
+  load_boxes = boxes;
+  load_cuts = cuts;
+  load_cap = capacity;
+  load_total = 0;
+  load_vals.assign((size_t)capacity * load_plan.nlists(), 0.0);
+  load_times.assign((size_t)capacity, 0.0);
+}
+
+void CpuSolver::clear_load_history() { load_total = 0; }
+
+LoadHistory CpuSolver::load_history() {
+  if (load_cap == 0) throw std::runtime_error("load_history: no recorder armed (record_loads)");
+  return load_history_from_ring(load_plan, load_vals.data(), load_total, load_cap,
+                                [&](long s) { return load_times[s]; });
+}
+
 // the values download() would put into the records now: the lean inviscid
 // state keeps its pressure in P2 (lean_materialize_cell copies it to p)
 void CpuSolver::start_averaging(int every, bool second_moments, bool step_weight, bool favre,
@@ -938,6 +971,7 @@ void CpuSolver::after_step() {
       }
     }
   }
+  if (load_cap) record_loads_step();
   if (probe_cap == 0) return;
   const size_t np = probe_idx.size();
   const long slot = probe_total % probe_cap;
@@ -953,6 +987,31 @@ void CpuSolver::after_step() {
   }
   probe_times[slot] = cs.global_time + cur_time_part;
   probe_total++;
+}
+
+// the lists of the plan from the arrays download() would copy, each folded in list order
+void CpuSolver::record_loads_step() {
+  const LoadPlan& L = load_plan;
+  const long slot = load_total % load_cap;
+  const real* p = lean_state ? P2[pbuf].data() : h.p.data();
+  const real* ru = h.S[0].data() + (size_t)I_RHOU * h.N;
+  const real* gU = h.grad.data() + (size_t)G_DUDY * h.N;
+  const real* gV = h.grad.data() + (size_t)G_DVDX * h.N;
+  real* row = &load_vals[(size_t)slot * L.nlists()];
+  for (int l = 0; l < L.nlists(); l++) {
+    real s = 0;
+    for (long t = L.off[l]; t < L.off[l + 1]; t++) {
+      const long c = L.cell[t], c2 = L.cell2[t];
+      const int k = L.kind[t];
+      const real a = k == LK_M ? ru[c] : p[c];
+      const real g = k == LK_FY ? gV[c] : gU[c];
+      const real nb = k == LK_FY ? h.V[pbuf][c2] : h.U[pbuf][c2];
+      s += load_term(k, L.coef[t], a, h.mu[c], h.mu_t[c], g, nb);
+    }
+    row[l] = s;
+  }
+  load_times[slot] = cs.global_time + cur_time_part;
+  load_total++;
 }
 
 ProbeHistory CpuSolver::probe_history() {
@@ -987,6 +1046,8 @@ void CpuSolver::upload() {
   lean_ok = lean_eligible(cs, &lean_why);
   lean_sg_ok = lean_ok && lean_single_gas(cs);
   lean_state = 0;
+  // (the records were replaced: the armed load recorder's cells follow their flags)
+  if (load_cap) load_plan = build_load_plan(cs, cs.J, load_boxes, load_cuts, l_off);
   if (lean_ok) {
     lb = lean_flags(h, cs.cfg.ProblemType);
     for (int b = 0; b < 2; b++) {

@@ -22,6 +22,7 @@
 #include "residual.hpp"
 #include "lean_euler.hpp"
 #include "flow_stats.hpp"
+#include "load_plan.hpp"
 
 namespace hf2d {
 
@@ -243,6 +244,21 @@ class SolverBase {
   // start_averaging's argument check (nsp: the backend's mechanism species, 0 outside mechanism mode)
   static void check_averaging(int every, const std::vector<int>& species, int nsp);
 
+  // Opt-in per-step load recorder (core/load_plan.hpp): after every step the
+  // pressure and friction folds of x_force_terms / y_force_terms of each box
+  // (x0, y0, dx, dy) and mass_flow_rate_x of each cut (x0, y0, dy), bit for
+  // bit what the host functions give on a field downloaded after that step,
+  // and the step's time go into a ring of `capacity` rows.  Arming again
+  // replaces the recorder and restarts the count.  std::invalid_argument: no
+  // box and no cut, more than LOAD_MAX of either, capacity < 1, a number that
+  // is not finite.  std::runtime_error: a solver that is one strip of several,
+  // or a backend without a recorder.
+  virtual void record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity);
+  virtual LoadHistory load_history();
+  virtual void clear_load_history();
+  // record_loads' checks: the arguments, and that this solver holds the whole field
+  void check_record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) const;
+
  protected:
   // called by advance() after a step the host completed (not the device's asynchronous ones)
   virtual void after_step() {}
@@ -300,6 +316,18 @@ class CpuSolver : public SolverBase {
   bool avg_favre = false;
   std::vector<double> avg_m;   // every plane (stats_plane_count): m [STATS_VARS][N], M [STATS_VARS][N], C [N], then avg_x's
   StatsExt avg_x;              // species list and the extension's planes inside avg_m
+
+  // host load recorder: evaluates the plan on the arrays download() reads
+  void record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) override;
+  LoadHistory load_history() override;
+  void clear_load_history() override;
+  LoadPlan load_plan;
+  std::vector<LoadBox> load_boxes;
+  std::vector<LoadCut> load_cuts;
+  long load_cap = 0, load_total = 0;
+  void record_loads_step();         // after_step, while armed
+  std::vector<real> load_vals;      // [load_cap][nlists]
+  std::vector<double> load_times;   // [load_cap]
 
   HostArrays h;
   int gi0, gi1;     // owned global columns

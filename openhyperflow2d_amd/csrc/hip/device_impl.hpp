@@ -119,6 +119,15 @@ struct DeviceSolver::Impl {
   long* probe_idx = nullptr;   // K8 monitor probes (sample_monitors)
   real* probe_out = nullptr;
   ProbeRing ring{};            // per-step recorder (record_probes); cap == 0: not armed
+  LoadsDev loads{};            // per-step load recorder (record_loads); cap == 0: not armed
+  // ... its device arrays and their sizes (arming again or a plan rebuilt by upload reuses what fits)
+  long *loads_cell = nullptr, *loads_cell2 = nullptr, *loads_off = nullptr;
+  real *loads_coef = nullptr, *loads_scratch = nullptr, *loads_vals = nullptr;
+  uint8_t* loads_kind = nullptr;
+  double* loads_times = nullptr;
+  long loads_terms_cap = 0;
+  int loads_off_cap = 0;
+  size_t loads_vals_cap = 0, loads_times_cap = 0;
   FlowStats stats{};           // whole-field statistics (start_averaging)
   size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
   size_t stats_used = 0;       // of which the armed options use (stats_plane_count)

@@ -443,6 +443,8 @@ void DeviceSolver::upload() {
   sbuf = 0;
   dsbuf = 0;
   pbuf = 0;
+  // (the records were replaced: the armed load recorder's cells follow their flags)
+  if (loads_cap) loads_plan_rebuild();
 }
 
 void DeviceSolver::set_lean_plain(bool on) {
@@ -522,6 +524,14 @@ void DeviceSolver::on_cycle_roll() {
     HIP_CHECK(hipStreamSynchronize(m.stream));
     for (double& t : tp) t -= T;
     HIP_CHECK(hipMemcpyAsync(m.ring.times, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+  }
+  if (loads_cap) {
+    std::vector<double> tp((size_t)loads_cap);
+    HIP_CHECK(hipMemcpyAsync(tp.data(), m.loads.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    for (double& t : tp) t -= T;
+    HIP_CHECK(hipMemcpyAsync(m.loads.times, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
     HIP_CHECK(hipStreamSynchronize(m.stream));
   }
   if (stats_armed) {
@@ -646,7 +656,9 @@ uint64_t DeviceSolver::mode_signature() const {
                        // captured before arming again writes the previous ring)
                        probe_gen,
                        // (likewise the accumulator's two launches: start / stop_averaging)
-                       stats_gen};
+                       stats_gen,
+                       // (and the load recorder's: record_loads, a plan rebuilt by upload)
+                       loads_gen};
   for (int f : state) mix(f);
   return h;
 }
@@ -830,6 +842,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   if (!cs.cfg.isAdiabaticWall) wall_heat(c);
   if (probe_cap) launch_probe_record(P);
   if (stats_on) launch_stats(P);
+  if (loads_cap) launch_loads(P, c.slot, c.slot_next);
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;
   StepResult r;
@@ -877,6 +890,8 @@ std::string DeviceSolver::autotune(int steps) {
   probe_cap = 0;
   const bool s_stats = stats_on;   // (nor does the accumulator take them as samples)
   stats_on = false;
+  const long s_loads = loads_cap;  // (nor the load recorder)
+  loads_cap = 0;
   struct Cand {
     int cpt, tj, nt, wgcu = 0;
   };
@@ -1007,6 +1022,7 @@ std::string DeviceSolver::autotune(int steps) {
   last_res_valid = s_resv;
   probe_cap = s_probe;
   stats_on = s_stats;
+  loads_cap = s_loads;
   upload();   // device scalars from the restored host state
   graph_launches = 0;
   lns_steps = lnm_steps = 0;   // (the tuning steps do not count as the run's)

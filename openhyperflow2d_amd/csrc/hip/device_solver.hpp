@@ -118,6 +118,12 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void reset_averaging() override;
   void stop_averaging() override;
   FlowAverages averages() override;
+  // per-step load recorder (hip/load_history.hpp): hf2d_loads_terms and
+  // hf2d_loads_fold follow the step while armed; reading the history neither
+  // leaves the lean state nor changes a ping-pong parity
+  void record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) override;
+  LoadHistory load_history() override;
+  void clear_load_history() override;
   void trace_push(const char* name) override;
   void trace_pop() override;
   void synchronize();
@@ -250,6 +256,12 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   bool stats_favre = false;
   std::vector<int> stats_species;   // mechanism indices of the listed species
   int stats_gen = 0;            // arming generation (mode_signature, as probe_gen)
+  int loads_gen = 0;            // arming generation (mode_signature, as probe_gen)
+  long loads_cap = 0;           // 0: not armed
+  bool loads_friction = false;  // the armed plan holds friction terms: the split fills store their gradients every step
+  LoadPlan loads_plan;          // host copy of the armed plan
+  std::vector<LoadBox> loads_boxes;
+  std::vector<LoadCut> loads_cuts;
   bool fx_pending = false;   // fused tile steps left the newest ghost columns and dt in the mailbox (p2p_complete)
   // fused lean N-S steps: the last step's halo is still in the mailbox; the
   // next fused step's edge tiles unpack it (lns_ghost_prologue)
@@ -270,6 +282,11 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void run_graph();
   void launch_probe_record(const StepParams& P);   // end of do_step_eager, post-step buffers
   void launch_stats(const StepParams& P);          // after it
+  void launch_loads(const StepParams& P, int slot, int slot_next);   // the load recorder's two launches
+  LoadPlan loads_plan_build(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts) const;
+  void loads_plan_upload(LoadPlan&& P);            // a built plan -> device
+  void loads_plan_rebuild();                       // the armed boxes / cuts over the records upload() replaced
+  void lns_fill_views(SoA& sin, SoA& out) const;   // the views lns_materialize's fill would run over now
   int post_step_view(SoA& s) const;                // PR_* kind and view both of them read
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)
   // One step (do_step_eager): the kernels that run it, what every path reads

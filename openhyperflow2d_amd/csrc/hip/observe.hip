@@ -1,8 +1,10 @@
 // Observers of the run: monitor points, the per-step probe recorder
-// (probe_history.hpp) and the time-averaged flow statistics (flow_stats.hpp).
+// (probe_history.hpp), the per-step load recorder (load_history.hpp) and the
+// time-averaged flow statistics (flow_stats.hpp).
 
 #include "device_impl.hpp"
 #include "flow_stats.hpp"
+#include "load_history.hpp"
 
 namespace hf2d {
 
@@ -190,6 +192,198 @@ void DeviceSolver::launch_probe_record(const StepParams& P) {
     case PR_LEAN: hipLaunchKernelGGL(hf2d_probe_record<PR_LEAN>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
     default: hipLaunchKernelGGL(hf2d_probe_record<PR_GATHER>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
   }
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Per-step load recorder (hip/load_history.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) {
+  check_record_loads(boxes, cuts, capacity);   // (the arguments; one strip of several refuses)
+  Impl& m = *impl;
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  // (a refused plan throws here and leaves the armed recorder, if any, whole:
+  // its boxes, cuts, plan and ring are replaced only together, below)
+  LoadPlan P = loads_plan_build(boxes, cuts);
+  const int cap = (int)std::min<long>(capacity, 0x7fffffffL);
+  const size_t nv = (size_t)cap * P.nlists();
+  LoadsDev& L = m.loads;
+  // (arrays that are large enough are used again: arming over and over does not grow device memory)
+  if (nv > m.loads_vals_cap) {
+    m.loads_vals = m.mem.alloc<real>(nv);
+    m.loads_vals_cap = nv;
+  }
+  if ((size_t)cap > m.loads_times_cap) {
+    m.loads_times = m.mem.alloc<double>((size_t)cap);
+    m.loads_times_cap = (size_t)cap;
+  }
+  if (!L.count) L.count = m.mem.alloc<unsigned long long>(1);
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  loads_cap = 0;
+  loads_plan_upload(std::move(P));
+  loads_boxes = boxes;
+  loads_cuts = cuts;
+  L.vals = m.loads_vals;
+  L.times = m.loads_times;
+  L.cap = cap;
+  HIP_CHECK(hipMemsetAsync(L.count, 0, sizeof(unsigned long long), m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  loads_cap = cap;
+}
+
+// The plan of the boxes and cuts over the records the backend holds now.
+// Throws where a term could not be evaluated exactly.
+LoadPlan DeviceSolver::loads_plan_build(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts) const {
+  LoadPlan P = build_load_plan(cs, cs.J, boxes, cuts, l_off);
+  for (long c : P.cell)
+    if (c < 0 || c >= h.N) throw std::runtime_error("load recorder: a term's cell lies outside the solver's arrays");
+  for (long c : P.cell2)
+    if (c < 0 || c >= h.N) throw std::runtime_error("load recorder: a term's cell lies outside the solver's arrays");
+  // the lean N-S / mechanism kinds fill a wall node with the parameters of the
+  // recorded step; the fill a download runs takes the next step's, whose
+  // is_mu_t differs after the last step before TurbStartIter.  That step is a
+  // lean one only where the steps before it are (lns_step_ok: no is_init, the
+  // same is_mu_t as the step before).  lns_ok / lnm_ok are what upload() found
+  // eligible, whatever the lean_ns / lean_mech switches say now or later, and
+  // an iteration count at or past TurbStartIter stays there, so the answer
+  // holds for every later step; upload() asks again for the plan it rebuilds.
+  // (the lean mechanism state exists for at most LNM_NSB = 9 species, the
+  // block loads_wall_fill runs the fill with: lnm_ok)
+  const bool box_terms = P.off[(size_t)LOAD_PARTS * P.nboxes] > 0;
+  if (box_terms && (lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset &&
+      cs.cfg.TurbStartIter >= 2 && last_iter + iter < (long)cs.cfg.TurbStartIter)
+    throw std::runtime_error("load recorder: wall terms on the lean N-S / mechanism state cannot be recorded exactly "
+                             "before TurbStartIter has passed; arm (or upload) later");
+  return P;
+}
+
+// A built plan into the device arrays (used again where they are large
+// enough; the stream is idle: flush_pending / upload synchronised it).
+void DeviceSolver::loads_plan_upload(LoadPlan&& P) {
+  Impl& m = *impl;
+  const long nt = P.nterms();
+  const int nl = P.nlists();
+  if (nt > m.loads_terms_cap) {
+    m.loads_cell = m.mem.alloc<long>((size_t)nt);
+    m.loads_cell2 = m.mem.alloc<long>((size_t)nt);
+    m.loads_coef = m.mem.alloc<real>((size_t)nt);
+    m.loads_kind = m.mem.alloc<uint8_t>((size_t)nt);
+    m.loads_scratch = m.mem.alloc<real>((size_t)nt);
+    m.loads_terms_cap = nt;
+  }
+  if (nl + 1 > m.loads_off_cap) {
+    m.loads_off = m.mem.alloc<long>((size_t)nl + 1);
+    m.loads_off_cap = nl + 1;
+  }
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets, and nothing in flight reads the arrays)
+  auto cp = [&](void* d, const void* s, size_t bytes) {
+    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, m.stream));
+  };
+  cp(m.loads_cell, P.cell.data(), nt * sizeof(long));
+  cp(m.loads_cell2, P.cell2.data(), nt * sizeof(long));
+  cp(m.loads_coef, P.coef.data(), nt * sizeof(real));
+  cp(m.loads_kind, P.kind.data(), nt * sizeof(uint8_t));
+  cp(m.loads_off, P.off.data(), ((size_t)nl + 1) * sizeof(long));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  LoadsDev& L = m.loads;
+  L.cell = m.loads_cell;
+  L.cell2 = m.loads_cell2;
+  L.coef = m.loads_coef;
+  L.kind = m.loads_kind;
+  L.off = m.loads_off;
+  L.scratch = m.loads_scratch;
+  L.nterms = nt;
+  L.nlists = nl;
+  loads_plan = std::move(P);
+  loads_friction = loads_plan.friction();
+  loads_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+// upload() replaced the records under an armed recorder: the same boxes and
+// cuts over the new flags (as many lists as before: the ring keeps its shape).
+void DeviceSolver::loads_plan_rebuild() { loads_plan_upload(loads_plan_build(loads_boxes, loads_cuts)); }
+
+void DeviceSolver::clear_load_history() {
+  if (!loads_cap) return;
+  flush_pending();
+  Impl& m = *impl;
+  HIP_CHECK(hipMemsetAsync(m.loads.count, 0, sizeof(unsigned long long), m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+LoadHistory DeviceSolver::load_history() {
+  if (!loads_cap) throw std::runtime_error("load_history: no recorder armed (record_loads)");
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const LoadsDev& L = m.loads;
+  unsigned long long total = 0;
+  std::vector<real> vals((size_t)L.cap * L.nlists);
+  std::vector<double> tp((size_t)L.cap);
+  HIP_CHECK(hipMemcpyAsync(&total, L.count, sizeof total, hipMemcpyDeviceToHost, m.stream));
+  if (!vals.empty())
+    HIP_CHECK(hipMemcpyAsync(vals.data(), L.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipMemcpyAsync(tp.data(), L.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  // (the probe ring's clock: probe_history)
+  return load_history_from_ring(loads_plan, vals.data(), (long)total, (long)L.cap, [&](long s) {
+    const real part = tp[s] - time_offset;
+    return (double)(cs.global_time + part);
+  });
+}
+
+// The views the fill of lns_materialize would run over now (its sin == pold
+// and its out), without running it.
+void DeviceSolver::lns_fill_views(SoA& sin, SoA& out) const {
+  const Impl& m = *impl;
+  const Impl::Levels x = m.levels();
+  sin = m.view(h, 1 - sbuf, abuf, dsbuf, 1 - pbuf);
+  if (m.mech) {
+    m.mech_view(sin, sbuf, dsbuf);
+    sin.mu = x.mu[1 - cbuf];
+    sin.lam = x.lam[1 - cbuf];
+    sin.mu_t = x.mu_t[1 - cbuf];
+    sin.CP = x.CP[cbuf];
+    sin.kk = x.kk[cbuf];
+    sin.p = x.p[cbuf];
+  } else {
+    sin.CP = x.CP[1 - cbuf];
+    sin.mu = x.mu[1 - cbuf];
+    sin.lam = x.lam[1 - cbuf];
+    sin.kk = x.kk[1 - cbuf];
+    sin.mu_t = x.mu_t[1 - cbuf];
+  }
+  out = m.view(h, sbuf, abuf, dsbuf, pbuf);
+}
+
+// After the other observers' launches; the same view, and for the lean N-S /
+// mechanism state the materialise fill's.  Nothing here allocates, copies or
+// synchronises.
+void DeviceSolver::launch_loads(const StepParams& P, int slot, int slot_next) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
+  SoA fin = s, out = s;
+  // the dt slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3, else (nstep + 2) % 3)
+  int fslot = slot;
+  if (lns_state) {
+    lns_fill_views(fin, out);
+    if (kind == PR_SGL) fslot = slot_next;
+  }
+  const LoadsDev& L = m.loads;
+  if (L.nterms > 0) {
+    const dim3 g((unsigned)((L.nterms + LOADS_BLOCK - 1) / LOADS_BLOCK)), b(LOADS_BLOCK);
+    switch (kind) {
+      case PR_SGL: hipLaunchKernelGGL(hf2d_loads_terms<PR_SGL>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_SGT: hipLaunchKernelGGL(hf2d_loads_terms<PR_SGT>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_MECH: hipLaunchKernelGGL(hf2d_loads_terms<PR_MECH>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      default: hipLaunchKernelGGL(hf2d_loads_terms<PR_GATHER>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(hf2d_loads_fold, dim3(1), dim3(LOADS_FOLD_WAVES * WAVE), 0, m.stream, L, m.sc);
   HIP_CHECK(hipGetLastError());
 }
 

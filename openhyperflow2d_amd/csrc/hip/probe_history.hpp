@@ -77,29 +77,14 @@ struct ProbeOwnIO {
   HF_HD real Ysn(int, int) const { return 0.0; }
 };
 
-// Row of one node.  `s` by kind:
-//   PR_GATHER  S, U, V, Tg, p: the current arrays
-//   PR_SGL/T   the materialise fill's input view (Sp^{m+1}, level-m fields)
-//   PR_MECH    S = Sp^{m+1}, U / V / kk = the lagged level, Tg / p = the
-//              stored state of the new level
+// Own-cell part of the materialise fill of one node into `c` (lean N-S /
+// mechanism kinds; shared with the load recorder, load_history.hpp): c.S, c.U,
+// c.V, and for PR_SGL / PR_SGT also c.Tg, c.p.  `s` as probe_row's.  false:
+// the fill carries the node early (solid / unset: only c.S is formed).
 template <int KIND>
-HF_HD inline void probe_row(const StepParams& P, const SoA& s, long idx, real* row) {
+HF_HD inline bool probe_own_cell(const StepParams& P, const SoA& s, long idx, CellLocal& c) {
   const long N = s.N;
-  if (KIND == PR_GATHER) {
-    row[0] = s.p[idx];
-    row[1] = s.Tg[idx];
-    row[2] = s.S[idx];
-    row[3] = s.U[idx];
-    row[4] = s.V[idx];
-  } else if (KIND == PR_LEAN) {
-    const real p = s.p[idx], rho = s.S[idx];
-    row[0] = p;
-    row[1] = hf_div(hf_div(p, s.R[idx]), rho);   // lean_cell's Tg
-    row[2] = rho;
-    row[3] = s.U[idx];
-    row[4] = s.V[idx];
-  } else if (KIND == PR_MECH) {
-    CellLocal c;
+  if (KIND == PR_MECH) {
 #pragma unroll
     for (int k = 0; k < NEQ; k++) {
       c.S[k] = k < 4 ? s.S[k * N + idx] : 0.0;
@@ -115,21 +100,51 @@ HF_HD inline void probe_row(const StepParams& P, const SoA& s, long idx, real* r
     c.BGY = s.BGY[idx];
     c.Uw = c.Vw = 0.0;
     if (fill_node_pre(c)) fill_node_wall(c, P.fpa);
+    return true;
+  } else {
+    constexpr int MODE = KIND == PR_SGT ? SK_SGT : SK_SGL;
+    const int i = (int)(idx / P.ny), j = (int)(idx - (long)i * P.ny);
+    ProbeOwnIO io(s, idx);
+    real mY[1], mgx[1], mgy[1];
+    bool early, filled;
+    int neg = 0;
+    (void)fill_compute<MODE, 1, ProbeOwnIO, true>(P, io, c, mY, mgx, mgy, nullptr, 0, i, j, true, &neg, &early,
+                                                    &filled);
+    return !early;
+  }
+}
+
+// Row of one node.  `s` by kind:
+//   PR_GATHER  S, U, V, Tg, p: the current arrays
+//   PR_SGL/T   the materialise fill's input view (Sp^{m+1}, level-m fields)
+//   PR_MECH    S = Sp^{m+1}, U / V / kk = the lagged level, Tg / p = the
+//              stored state of the new level
+template <int KIND>
+HF_HD inline void probe_row(const StepParams& P, const SoA& s, long idx, real* row) {
+  if (KIND == PR_GATHER) {
+    row[0] = s.p[idx];
+    row[1] = s.Tg[idx];
+    row[2] = s.S[idx];
+    row[3] = s.U[idx];
+    row[4] = s.V[idx];
+  } else if (KIND == PR_LEAN) {
+    const real p = s.p[idx], rho = s.S[idx];
+    row[0] = p;
+    row[1] = hf_div(hf_div(p, s.R[idx]), rho);   // lean_cell's Tg
+    row[2] = rho;
+    row[3] = s.U[idx];
+    row[4] = s.V[idx];
+  } else if (KIND == PR_MECH) {
+    CellLocal c;
+    (void)probe_own_cell<KIND>(P, s, idx, c);
     row[0] = s.p[idx];
     row[1] = s.Tg[idx];
     row[2] = c.S[I_RHO];
     row[3] = c.U;
     row[4] = c.V;
   } else {
-    constexpr int MODE = KIND == PR_SGT ? SK_SGT : SK_SGL;
-    const int i = (int)(idx / P.ny), j = (int)(idx - (long)i * P.ny);
-    ProbeOwnIO io(s, idx);
     CellLocal c;
-    real mY[1], mgx[1], mgy[1];
-    bool early, filled;
-    int neg = 0;
-    (void)fill_compute<MODE, 1, ProbeOwnIO, true>(P, io, c, mY, mgx, mgy, nullptr, 0, i, j, true, &neg, &early,
-                                                    &filled);
+    const bool early = !probe_own_cell<KIND>(P, s, idx, c);
     // (a solid / unset node is refused at arming: the fill of any other node
     // recovers U, V, T, p unless it is skipped, and a skipped node stops the
     // lean step itself, LNS_SKIP_ERR)

@@ -95,4 +95,20 @@ struct ProbeRing {
   unsigned long long* count = nullptr;   // rows written since arming
 };
 
+// Per-step load recorder (load_history.hpp): the plan, one entry per term, and the ring
+struct LoadsDev {
+  // the plan (LoadPlan), one entry per term
+  const long* cell = nullptr;
+  const long* cell2 = nullptr;
+  const real* coef = nullptr;
+  const uint8_t* kind = nullptr;
+  const long* off = nullptr;   // [nlists + 1]
+  long nterms = 0;
+  int nlists = 0, cap = 0;
+  real* scratch = nullptr;     // [nterms] the step's term values
+  real* vals = nullptr;        // [cap][nlists]
+  double* times = nullptr;     // [cap] DevScalars::time_part after the step
+  unsigned long long* count = nullptr;   // rows written since arming
+};
+
 }  // namespace hf2d

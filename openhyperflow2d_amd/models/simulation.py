@@ -45,6 +45,7 @@ def parse_fault(spec: str):
 
 
 PROBE_VARS = ("p", "T", "rho", "U", "V")   # column order of Simulation.probe_history()["values"]
+LOAD_PARTS = ("Fx_p", "Fx_d", "Fy_p", "Fy_d")   # last axis of Simulation.load_history()["forces"]
 
 
 class Simulation:
@@ -135,6 +136,52 @@ class Simulation:
     def clear_probe_history(self) -> None:
         """Drop the recorded rows; the recorder stays armed on the same cells."""
         self.solver.clear_probe_history()
+
+    # -- per-step load recorder ---------------------------------------------
+    def record_loads(self, boxes=(), cuts=(), capacity: int = 4096) -> None:
+        """Arm the per-step load recorder on ``boxes`` ``(x0, y0, dx, dy)`` (the
+        arguments of ``Case.x_force`` / ``y_force``) and ``cuts`` ``(x0, y0, dy)``
+        (those of ``Case.mass_flow_x``): at most 16 of each, at least one of
+        either.
+
+        From now on every step appends, to a ring of ``capacity`` rows kept by
+        the backend, the four parts ``LOAD_PARTS = ("Fx_p", "Fx_d", "Fy_p",
+        "Fy_d")`` of every box (the pressure and the friction sum of the x and
+        of the y force), the mass flow through every cut and the step's time.
+        Every sum adds its terms in the order of the host integrals, so
+        ``Fx_p + Fx_d`` is bit for bit ``case.x_force(*box)`` on a field
+        downloaded after that step, ``Fy_p + Fy_d`` is ``case.y_force(*box)``
+        and the mass flow is ``case.mass_flow_x(*cut)``.  On the GPU two small
+        kernels run at the end of each step, inside the step graphs, and the
+        lean states are never materialised.  Arming again replaces the ring.
+        ``ValueError``: no box and no cut, more than 16 of either, ``capacity <
+        1`` or a number that is not finite.  ``RuntimeError``: the solver is
+        one strip of several (a one-process run only)."""
+        b = [tuple(float(v) for v in q) for q in boxes]
+        c = [tuple(float(v) for v in q) for q in cuts]
+        if any(len(q) != 4 for q in b) or any(len(q) != 3 for q in c):
+            raise ValueError("record_loads: a box is (x0, y0, dx, dy), a cut is (x0, y0, dy)")
+        self.solver.record_loads(b, c, int(capacity))
+
+    def load_history(self) -> dict:
+        """The recorded rows, oldest first: ``times`` [n] (the clock of
+        ``probe_history()``), ``forces`` [n, nboxes, 4] in ``LOAD_PARTS`` order,
+        ``mass_flow`` [n, ncuts], ``terms`` (the static number of terms of
+        every sum: ``box_terms`` [nboxes, 4], ``cut_terms`` [ncuts]), ``span``
+        [nboxes] (the wall span of each box, static:
+        ``Cx = (Fx_p + Fx_d) / body_pmax(span, flow)``) and ``total`` (steps
+        recorded since arming; n = min(total, capacity)).  Reading does not
+        disturb the solver state."""
+        h = dict(self.solver.load_history())
+        for k in ("times", "forces", "mass_flow", "span"):
+            h[k] = np.asarray(h[k])
+        h["terms"] = {k: np.asarray(v) for k, v in dict(h["terms"]).items()}
+        h["total"] = int(h["total"])
+        return h
+
+    def clear_load_history(self) -> None:
+        """Drop the recorded rows; the recorder stays armed on the same boxes and cuts."""
+        self.solver.clear_load_history()
 
     # -- time-averaged flow statistics ---------------------------------------
     def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time",
