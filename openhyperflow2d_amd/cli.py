@@ -7,6 +7,7 @@
                                      [--transport p2p|rccl]
                                      [--probe-history FILE.npz [--probe-capacity N]]
                                      [--load-history FILE.npz [--load-capacity N]]
+                                     [--wall-heat FILE.npz [--wall-heat-every K] [--wall-heat-capacity N]]
                                      [--averages FILE.npz [--averages-every K] [--averages-favre]
                                       [--averages-species all|A,B,...]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
@@ -50,6 +51,11 @@ def _cmd_run(a) -> int:
     if a.load_history and world > 1:
         if rank == 0:
             print("--load-history records in one process only; this is a %d-rank launch "
+                  "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
+        return 2
+    if a.wall_heat and world > 1:
+        if rank == 0:
+            print("--wall-heat records in one process only; this is a %d-rank launch "
                   "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
         return 2
     if a.averages and world > 1:
@@ -100,6 +106,15 @@ def _cmd_run(a) -> int:
         except (ValueError, RuntimeError) as e:
             print("--load-history: %s" % e, file=sys.stderr, flush=True)
             return 2
+    if a.wall_heat:
+        # the deck's own profiles, every K-th step: X only where the driver writes HeatFlux-X
+        keys = sim.case.wall_heat_keys
+        try:
+            sim.record_wall_heat(x=bool(keys["isOutHeatFluxX"]), y=True, every=a.wall_heat_every,
+                                 capacity=a.wall_heat_capacity)
+        except (ValueError, RuntimeError) as e:
+            print("--wall-heat: %s" % e, file=sys.stderr, flush=True)
+            return 2
     if a.averages:
         try:
             sp = a.averages_species
@@ -141,6 +156,17 @@ def _cmd_run(a) -> int:
         print("load history: %d of %d steps x %d boxes, %d cuts -> %s" % (h["times"].shape[0], h["total"],
                                                                            len(load_boxes), len(load_cuts),
                                                                            a.load_history), flush=True)
+    if a.wall_heat:
+        import numpy as np
+
+        from .models.simulation import WALL_HEAT_X
+
+        h = sim.wall_heat_history()
+        with open(a.wall_heat, "wb") as f:   # (np.savez on a path would append ".npz")
+            np.savez(f, vars=np.asarray(WALL_HEAT_X), **{k: np.asarray(v) for k, v in h.items()})
+        print("wall heat: %d of %d samples x (4 x %d + %d) entries -> %s" % (h["times"].shape[0], h["total"],
+                                                                            h["x"].shape[2], h["y"].shape[1],
+                                                                            a.wall_heat), flush=True)
     if a.averages:
         import numpy as np
 
@@ -254,6 +280,15 @@ def main(argv=None) -> int:
                         "mass_flow / box_terms / cut_terms / span / total / boxes / cuts / parts to this file")
     r.add_argument("--load-capacity", dest="load_capacity", type=int, default=4096, metavar="N",
                    help="rows the load recorder keeps: the last N steps (default 4096)")
+    r.add_argument("--wall-heat", dest="wall_heat", metavar="FILE.npz",
+                   help="record the HeatFlux-X profile (Q, Alpha, Cp, St per column; only when isOutHeatFluxX is set) "
+                        "and the HeatFlux-Y profile with the deck's Cp_Flow_Index / y_min / y_max after every K-th "
+                        "step (one process only) and write times / x / y / total / x_nodes / y_nodes, the running "
+                        "mean_ / var_ / peak_ / peak_time_ of both, time, samples and vars to this file")
+    r.add_argument("--wall-heat-every", dest="wall_heat_every", type=int, default=1, metavar="K",
+                   help="sample every K-th step (default 1)")
+    r.add_argument("--wall-heat-capacity", dest="wall_heat_capacity", type=int, default=4096, metavar="N",
+                   help="rows the wall heat recorder keeps: the last N samples (default 4096; 0: statistics only)")
     r.add_argument("--averages", metavar="FILE.npz",
                    help="accumulate time-averaged p, T, rho, U, V, their variances and the U-V covariance over the "
                         "whole field at every step (one process only) and write mean / var / cov_uv / vars / time / "

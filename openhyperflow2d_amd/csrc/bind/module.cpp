@@ -566,7 +566,52 @@ PYBIND11_MODULE(_hf2d, m) {
         need_whole(c);
         if (!px.empty()) save_x_heat_flux(px, c, c.J);
         if (!py_.empty()) save_y_heat_flux(py_, c, c.J);
-      });
+      })
+      .def_property_readonly("wall_heat_keys",
+                             [](const Case& c) {   // the deck's heat-flux keys: record_wall_heat's defaults
+                               const Config& C = c.cfg;
+                               py::dict d;
+                               d["isOutHeatFluxX"] = C.isOutHeatFluxX;
+                               d["Cp_Flow_Index"] = C.Cp_Flow_index;
+                               d["y_min"] = C.y_min;
+                               d["y_max"] = C.y_max;
+                               d["isOutHeatFluxY"] = C.isOutHeatFluxY;
+                               d["flows"] = (int)c.flows2d.size();
+                               return d;
+                             })
+      .def("heat_flux_x",
+           [](const Case& c, py::object cp_flow, py::object rows) {
+             // the HeatFlux-X profile of the records: what save_heat_flux writes, as numbers
+             need_whole(c);
+             const Config& C = c.cfg;
+             const int f = cp_flow.is_none() ? C.Cp_Flow_index : cp_flow.cast<int>();
+             int y0 = C.y_min, y1 = C.y_max;
+             if (!rows.is_none()) {
+               const auto r = rows.cast<std::pair<int, int>>();
+               y0 = r.first;
+               y1 = r.second;
+             }
+             const py::ssize_t nx = c.J.nx;
+             py::array_t<real> a(std::vector<py::ssize_t>{(py::ssize_t)WALL_HEAT_X, nx});
+             real* q = a.mutable_data();
+             std::fill(q, q + WALL_HEAT_X * nx, (real)0);
+             if (!heat_flux_x_cols(c, c.J, 0, c.J.nx, f, y0, y1, q, q + nx, q + 2 * nx, q + 3 * nx))
+               throw py::value_error("heat_flux_x: Cp flow index " + std::to_string(f) + " outside the case's " +
+                                     std::to_string(c.flows2d.size()) + " flows");
+             return a;
+           },
+           py::arg("cp_flow") = py::none(), py::arg("rows") = py::none(),
+           "[4, nx] Q, Alpha, Cp, St of every column (heat_flux_x_cols); cp_flow: 1-based flow index (default: the "
+           "deck's Cp_Flow_Index), rows: (y_min, y_max) (default: the deck's)")
+      .def("heat_flux_y", [](const Case& c) {
+        need_whole(c);
+        std::vector<real> jq, Q(c.J.ny, 0.);
+        heat_flux_y_terms(c, c.J, 0, c.J.nx, jq);
+        fold_heat_flux_y(Q, jq);
+        py::array_t<real> a(std::vector<py::ssize_t>{(py::ssize_t)c.J.ny});
+        std::copy(Q.begin(), Q.end(), a.mutable_data());
+        return a;
+      }, "[ny] the HeatFlux-Y profile of the records (heat_flux_y_terms, fold_heat_flux_y)");
 
   m.def(
       "lean_tile_geom",
@@ -721,6 +766,69 @@ PYBIND11_MODULE(_hf2d, m) {
              return d;
            })
       .def("clear_load_history", &SolverBase::clear_load_history)
+      .def("record_wall_heat",
+           [](SolverBase& s, bool x, bool y, int cp_flow, int y_min, int y_max, int every, long capacity, bool statistics,
+              bool step_weight) {
+             WallHeatOpts o;
+             o.x = x;
+             o.y = y;
+             o.cp_flow = cp_flow;
+             o.y_min = y_min;
+             o.y_max = y_max;
+             o.every = every;
+             o.capacity = capacity;
+             o.statistics = statistics;
+             o.step_weight = step_weight;
+             s.record_wall_heat(o);
+           },
+           py::arg("x"), py::arg("y"), py::arg("cp_flow"), py::arg("y_min"), py::arg("y_max"), py::arg("every") = 1,
+           py::arg("capacity") = 1024, py::arg("statistics") = true, py::arg("step_weight") = false,
+           "arm the per-step wall heat recorder: the HeatFlux-X profile (Q, Alpha, Cp, St per column, flow cp_flow, "
+           "rows y_min / y_max) and the HeatFlux-Y profile after every `every`-th step")
+      .def("wall_heat_history",
+           [](SolverBase& s) {
+             WallHeatHistory H;
+             {
+               py::gil_scoped_release rel;
+               H = s.wall_heat_history();
+             }
+             const py::ssize_t n = (py::ssize_t)H.times.size(), nx = H.nx, ny = H.ny, ne = WALL_HEAT_X * nx + ny;
+             py::array_t<double> t(std::vector<py::ssize_t>{n});
+             py::array_t<real> x(std::vector<py::ssize_t>{n, (py::ssize_t)WALL_HEAT_X, nx});
+             py::array_t<real> y(std::vector<py::ssize_t>{n, ny});
+             py::array_t<long> xn(std::vector<py::ssize_t>{nx}), yn(std::vector<py::ssize_t>{ny});
+             std::copy(H.times.begin(), H.times.end(), t.mutable_data());
+             for (py::ssize_t k = 0; k < n; k++) {
+               const real* row = H.vals.data() + k * ne;
+               std::copy(row, row + WALL_HEAT_X * nx, x.mutable_data() + k * WALL_HEAT_X * nx);
+               std::copy(row + WALL_HEAT_X * nx, row + ne, y.mutable_data() + k * ny);
+             }
+             std::copy(H.x_nodes.begin(), H.x_nodes.end(), xn.mutable_data());
+             std::copy(H.y_nodes.begin(), H.y_nodes.end(), yn.mutable_data());
+             py::dict d;
+             d["times"] = t;
+             d["x"] = x;
+             d["y"] = y;
+             d["total"] = H.total;
+             d["x_nodes"] = xn;
+             d["y_nodes"] = yn;
+             if (H.statistics) {
+               const char* names[4] = {"mean", "var", "peak", "peak_time"};
+               const std::vector<double>* src[4] = {&H.mean, &H.var, &H.peak, &H.peak_time};
+               for (int q = 0; q < 4; q++) {
+                 py::array_t<double> ax(std::vector<py::ssize_t>{(py::ssize_t)WALL_HEAT_X, nx});
+                 py::array_t<double> ay(std::vector<py::ssize_t>{ny});
+                 std::copy(src[q]->begin(), src[q]->begin() + WALL_HEAT_X * nx, ax.mutable_data());
+                 std::copy(src[q]->begin() + WALL_HEAT_X * nx, src[q]->end(), ay.mutable_data());
+                 d[py::str(std::string(names[q]) + "_x")] = ax;
+                 d[py::str(std::string(names[q]) + "_y")] = ay;
+               }
+               d["time"] = H.time;
+               d["samples"] = H.samples;
+             }
+             return d;
+           })
+      .def("clear_wall_heat", &SolverBase::clear_wall_heat)
       .def("start_averaging", &SolverBase::start_averaging, py::arg("every") = 1, py::arg("second_moments") = true,
            py::arg("step_weight") = false, py::arg("favre") = false, py::arg("species") = std::vector<int>{},
            "arm the whole-field accumulator: weighted running mean (and variances, U-V covariance) of "

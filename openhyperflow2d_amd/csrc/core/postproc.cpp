@@ -1,4 +1,5 @@
 #include "postproc.hpp"
+#include "wall_heat.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -376,47 +377,37 @@ real average_temperature(const Case& cs, const Field& J, real x0, real l, real d
   return C.FT == FT_AXISYMMETRIC ? Tm / Vs : Tm / n;
 }
 
-static real near_lam(const Field& J, int i, int j, const CellRecord& n, int& cnt) {
+// lam_eff of node (i, j): lam + lam_t of the node and of N1..N4 (wall_heat.hpp)
+static real near_lam_eff(const Field& J, int i, int j, const CellRecord& n) {
   const int N1 = i - n.idXl, N2 = i + n.idXr, N3 = j + n.idYu, N4 = j - n.idYd;
-  real s = n.lam + n.lam_t;
-  cnt = 5;
-  s += J.at(N1, j).lam + J.at(N1, j).lam_t;
-  s += J.at(N2, j).lam + J.at(N2, j).lam_t;
-  s += J.at(i, N3).lam + J.at(i, N3).lam_t;
-  s += J.at(i, N4).lam + J.at(i, N4).lam_t;
-  return s;
+  return wall_heat_lam_eff(n.lam + n.lam_t, J.at(N1, j).lam + J.at(N1, j).lam_t, J.at(N2, j).lam + J.at(N2, j).lam_t,
+                           J.at(i, N3).lam + J.at(i, N3).lam_t, J.at(i, N4).lam + J.at(i, N4).lam_t);
 }
 
-bool heat_flux_x_cols(const Case& cs, const Field& J, int ib, int ie, real* Q, real* Al, real* Cp, real* St) {
-  const Config& C = cs.cfg;
-  if (C.Cp_Flow_index < 1 || C.Cp_Flow_index > (int)cs.flows2d.size()) return false;
-  const GasFlow& F = cs.flows2d[C.Cp_Flow_index - 1];
-  const real Trec = (1 + 0.45 * (F.kg() - 1.0) * F.flow_MACH() * F.flow_MACH()) * F.Tg();
+bool heat_flux_x_cols(const Case& cs, const Field& J, int ib, int ie, int cp_flow, int y_min, int y_max, real* Q,
+                      real* Al, real* Cp, real* St) {
+  WallHeatConst K;
+  if (!wall_heat_consts(cs, cp_flow, K)) return false;
+  const auto rows = wall_heat_rows(y_min, y_max, J.ny);
   for (int i = ib; i < ie; i++) {
     // the reference also keeps laminar-correlation maxima (QR, AR) and Re, Pr
     // for its _REF_TEST_ build; only the written columns are formed here
     Q[i] = Al[i] = Cp[i] = St[i] = 0.;
-    for (int j = std::max(0, C.y_min); j < std::min(C.y_max, J.ny - 1); j++) {
+    for (int j = rows.first; j < rows.second; j++) {
       const CellRecord& n = J.at(i, j);
       if (!n.is(CT_WALL_NO_SLIP)) continue;
-      int cnt;
-      const real lam_eff = near_lam(J, i, j, n, cnt) / cnt;
-      real q = lam_eff * (n.Tg - C.Ts0) / C.dy;
-      real alpha = lam_eff / C.dy;
-      const real st = q / (F.ROG() * F.Wg2d() * F.C * (Trec - C.Ts0));
-      const real cp = calc_cp(n, F);
-      if (Q[i] != 0.) {
-        Q[i] = std::max(Q[i], q);
-        Al[i] = std::max(Al[i], alpha);
-      } else {
-        Q[i] = q;
-        Al[i] = alpha;
-      }
-      Cp[i] = cp;
-      St[i] = st;
+      const WallHeatXTerm t = wall_heat_x_term(K, near_lam_eff(J, i, j, n), n.Tg, n.p);
+      wall_heat_fold_x(Q[i], Al[i], t.q, t.alpha);
+      Cp[i] = t.cp;
+      St[i] = t.st;
     }
   }
   return true;
+}
+
+bool heat_flux_x_cols(const Case& cs, const Field& J, int ib, int ie, real* Q, real* Al, real* Cp, real* St) {
+  const Config& C = cs.cfg;
+  return heat_flux_x_cols(cs, J, ib, ie, C.Cp_Flow_index, C.y_min, C.y_max, Q, Al, Cp, St);
 }
 
 void write_x_heat_flux(const std::string& path, const Config& C, bool valid, const real* Q, const real* Al,
@@ -436,24 +427,19 @@ void save_x_heat_flux(const std::string& path, const Case& cs, const Field& J) {
 }
 
 void heat_flux_y_terms(const Case& cs, const Field& J, int ib, int ie, std::vector<real>& jq) {
-  const Config& C = cs.cfg;
+  WallHeatConst K;
+  (void)wall_heat_consts(cs, 0, K);   // (Ts0 and the spacings; the Y profile reads no flow)
   for (int j = 0; j < J.ny; j++)
     for (int i = ib; i < std::min(ie, J.nx - 1); i++) {
       const CellRecord& n = J.at(i, j);
       if (!n.is(CT_WALL_NO_SLIP)) continue;
-      int cnt;
-      const real lam_eff = near_lam(J, i, j, n, cnt) / cnt;
       jq.push_back((real)j);
-      jq.push_back(lam_eff * (n.Tg - C.Ts0) / C.dx);
+      jq.push_back(wall_heat_q(K, near_lam_eff(J, i, j, n), n.Tg, K.dx));
     }
 }
 
 void fold_heat_flux_y(std::vector<real>& Q, const std::vector<real>& jq) {
-  for (size_t k = 0; k + 1 < jq.size(); k += 2) {
-    real& Qj = Q[(size_t)jq[k]];
-    const real q = jq[k + 1];
-    Qj = (Qj != 0.) ? std::max(Qj, q) : q;
-  }
+  for (size_t k = 0; k + 1 < jq.size(); k += 2) wall_heat_fold_y(Q[(size_t)jq[k]], jq[k + 1]);
 }
 
 void write_y_heat_flux(const std::string& path, const Config& C, const std::vector<real>& Q) {

@@ -34,6 +34,11 @@ void save_y_heat_flux(const std::string& path, const Case& cs, const Field& J);
 // (false: no valid Cp flow, header only) and the Y terms as (j, q) pairs in
 // the reference's (j, i) order, folded with its max-or-first rule
 bool heat_flux_x_cols(const Case& cs, const Field& J, int ib, int ie, real* Q, real* Al, real* Cp, real* St);
+// ... with the flow (1-based) and the rows' keys given instead of the deck's
+// Cp_Flow_Index, y_min, y_max.  The node's term and the fold are those of
+// wall_heat.hpp, shared with the per-step wall heat recorder.
+bool heat_flux_x_cols(const Case& cs, const Field& J, int ib, int ie, int cp_flow, int y_min, int y_max, real* Q,
+                      real* Al, real* Cp, real* St);
 void write_x_heat_flux(const std::string& path, const Config& C, bool valid, const real* Q, const real* Al,
                        const real* Cp, const real* St);
 void heat_flux_y_terms(const Case& cs, const Field& J, int ib, int ie, std::vector<real>& jq);

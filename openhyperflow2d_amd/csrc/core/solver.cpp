@@ -465,6 +465,21 @@ void SolverBase::record_loads(const std::vector<LoadBox>&, const std::vector<Loa
 LoadHistory SolverBase::load_history() { throw std::runtime_error("this backend has no per-step load recorder"); }
 void SolverBase::clear_load_history() {}
 
+void SolverBase::check_record_wall_heat(const WallHeatOpts& o) const {
+  check_wall_heat(o);
+  const auto own = owned_columns();
+  if (comm->size() > 1 || own.first != 0 || own.second != cs.J.nx || !cs.J.whole())
+    throw std::runtime_error("record_wall_heat: this solver is one strip of several; the per-step wall heat recorder "
+                             "needs a one-process run (the serial folds run over the whole field)");
+}
+void SolverBase::record_wall_heat(const WallHeatOpts&) {
+  throw std::runtime_error("this backend has no per-step wall heat recorder");
+}
+WallHeatHistory SolverBase::wall_heat_history() {
+  throw std::runtime_error("this backend has no per-step wall heat recorder");
+}
+void SolverBase::clear_wall_heat() {}
+
 void SolverBase::start_averaging(int, bool, bool, bool, const std::vector<int>&) {
   throw std::runtime_error("this backend has no flow-statistics accumulator");
 }
@@ -972,6 +987,7 @@ void CpuSolver::after_step() {
     }
   }
   if (load_cap) record_loads_step();
+  if (wq_armed) record_wall_heat_step();
   if (probe_cap == 0) return;
   const size_t np = probe_idx.size();
   const long slot = probe_total % probe_cap;
@@ -1014,6 +1030,67 @@ void CpuSolver::record_loads_step() {
   load_total++;
 }
 
+void CpuSolver::record_wall_heat(const WallHeatOpts& o) {
+  check_record_wall_heat(o);
+  // (a refused plan throws here and leaves the armed recorder, if any, whole)
+  WallHeatPlan P = build_wall_heat_plan(cs, cs.J, o, l_off);
+  wq_plan = std::move(P);
+  wq_opts = o;
+  wq_vals.assign((size_t)o.capacity * wq_plan.nentries(), 0.0);
+  wq_times.assign((size_t)o.capacity, 0.0);
+  wq_scratch.assign(3 * (size_t)wq_plan.ncells(), 0.0);
+  wq_armed = true;
+  clear_wall_heat();
+}
+
+// the ring and the statistics restart; the sampling count and the clock with them
+void CpuSolver::clear_wall_heat() {
+  if (!wq_armed) return;
+  wq_total = 0;
+  wq_sc = StatsScalars{};
+  wq_sc.every = wq_opts.every;
+  wq_sc.step_weight = wq_opts.step_weight ? 1 : 0;
+  wq_sc.t_seen = (double)(cs.global_time + cur_time_part);
+  wq_stat.assign(4 * (size_t)wq_plan.nentries(), 0.0);
+}
+
+// the needed cells from the arrays download() would copy, then every list folded in list order
+void CpuSolver::record_wall_heat_step() {
+  const double t = (double)(cs.global_time + cur_time_part);
+  if (!stats_tick(wq_sc, t)) return;
+  const WallHeatPlan& L = wq_plan;
+  const size_t nc = (size_t)L.ncells(), ne = (size_t)L.nentries();
+  const real* p = lean_state ? P2[pbuf].data() : h.p.data();
+  real *sl = wq_scratch.data(), *sT = sl + nc, *sp = sT + nc;
+  for (size_t k = 0; k < nc; k++) {
+    const long c = L.cells[k];
+    sl[k] = h.lam[c] + h.lam_t[c];
+    sT[k] = h.Tg[pbuf][c];
+    sp[k] = p[c];
+  }
+  const long cap = wq_opts.capacity;
+  const long slot = cap ? wq_total % cap : 0;
+  double *m = wq_stat.data(), *M = m + ne, *pk = M + ne, *pt = pk + ne;
+  for (int l = 0; l < L.nlists(); l++) {
+    real out[WALL_HEAT_X];
+    wall_heat_list(L.K, L.nx, l, L.off.data(), L.list.data(), L.node5.data(), sl, sT, sp, out);
+    for (int k = 0; k < (l < L.nx ? WALL_HEAT_X : 1); k++) {
+      const int e = wall_heat_entry(L.nx, l, k);
+      if (cap) wq_vals[(size_t)slot * ne + e] = out[k];
+      if (wq_opts.statistics)
+        wall_heat_stat(wq_sc.w, wq_sc.r, t, wq_sc.samples == 1, (double)out[k], m[e], M[e], pk[e], pt[e]);
+    }
+  }
+  if (cap) wq_times[slot] = t;
+  wq_total++;
+}
+
+WallHeatHistory CpuSolver::wall_heat_history() {
+  if (!wq_armed) throw std::runtime_error("wall_heat_history: no recorder armed (record_wall_heat)");
+  return wall_heat_history_from(wq_plan, wq_opts, wq_vals.data(), wq_times.data(), wq_total, wq_stat.data(), wq_sc,
+                                [](double t) { return t; });
+}
+
 ProbeHistory CpuSolver::probe_history() {
   if (probe_cap == 0) throw std::runtime_error("probe_history: no recorder armed (record_probes)");
   ProbeHistory H;
@@ -1048,6 +1125,10 @@ void CpuSolver::upload() {
   lean_state = 0;
   // (the records were replaced: the armed load recorder's cells follow their flags)
   if (load_cap) load_plan = build_load_plan(cs, cs.J, load_boxes, load_cuts, l_off);
+  if (wq_armed) {   // (likewise the wall heat recorder's nodes)
+    wq_plan = build_wall_heat_plan(cs, cs.J, wq_opts, l_off);
+    wq_scratch.assign(3 * (size_t)wq_plan.ncells(), 0.0);
+  }
   if (lean_ok) {
     lb = lean_flags(h, cs.cfg.ProblemType);
     for (int b = 0; b < 2; b++) {

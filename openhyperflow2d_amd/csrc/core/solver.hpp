@@ -23,6 +23,7 @@
 #include "lean_euler.hpp"
 #include "flow_stats.hpp"
 #include "load_plan.hpp"
+#include "wall_heat.hpp"
 
 namespace hf2d {
 
@@ -259,6 +260,22 @@ class SolverBase {
   // record_loads' checks: the arguments, and that this solver holds the whole field
   void check_record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) const;
 
+  // Opt-in per-step wall heat recorder (core/wall_heat.hpp): after every
+  // `every`-th step the HeatFlux-X profile (Q, Alpha, Cp, St per column) and
+  // the HeatFlux-Y profile (Q per row), bit for bit what heat_flux_x_cols /
+  // heat_flux_y_terms + fold_heat_flux_y give on a field downloaded after that
+  // step, and the step's time go into a ring of `capacity` rows (0: none), and
+  // with `statistics` into a running mean, variance, peak and peak time per
+  // entry.  Arming again replaces the recorder and restarts the count.
+  // std::invalid_argument: neither profile, every < 1, capacity < 0, the X
+  // profile with a flow index the case does not have.  std::runtime_error: a
+  // solver that is one strip of several, or a backend without a recorder.
+  virtual void record_wall_heat(const WallHeatOpts& o);
+  virtual WallHeatHistory wall_heat_history();
+  virtual void clear_wall_heat();
+  // record_wall_heat's checks: the options, and that this solver holds the whole field
+  void check_record_wall_heat(const WallHeatOpts& o) const;
+
  protected:
   // called by advance() after a step the host completed (not the device's asynchronous ones)
   virtual void after_step() {}
@@ -328,6 +345,21 @@ class CpuSolver : public SolverBase {
   void record_loads_step();         // after_step, while armed
   std::vector<real> load_vals;      // [load_cap][nlists]
   std::vector<double> load_times;   // [load_cap]
+
+  // host wall heat recorder: evaluates the plan on the arrays download() reads
+  void record_wall_heat(const WallHeatOpts& o) override;
+  WallHeatHistory wall_heat_history() override;
+  void clear_wall_heat() override;
+  bool wq_armed = false;
+  WallHeatOpts wq_opts;
+  WallHeatPlan wq_plan;
+  StatsScalars wq_sc;
+  long wq_total = 0;
+  void record_wall_heat_step();     // after_step, while armed
+  std::vector<real> wq_vals;        // [capacity][4 nx + ny]
+  std::vector<double> wq_times;     // [capacity]
+  std::vector<double> wq_stat;      // m, M, peak, peak_time: [4 nx + ny] each
+  std::vector<real> wq_scratch;     // lam + lam_t, Tg, p: [needed cells] each
 
   HostArrays h;
   int gi0, gi1;     // owned global columns

@@ -128,6 +128,14 @@ struct DeviceSolver::Impl {
   long loads_terms_cap = 0;
   int loads_off_cap = 0;
   size_t loads_vals_cap = 0, loads_times_cap = 0;
+  WallHeatDev wallq{};         // per-step wall heat recorder (record_wall_heat)
+  // ... its device arrays and their sizes (arming again or a plan rebuilt by upload reuses what fits)
+  long* wallq_cells = nullptr;
+  int *wallq_node5 = nullptr, *wallq_off = nullptr, *wallq_list = nullptr;
+  real *wallq_scratch = nullptr, *wallq_vals = nullptr;
+  double *wallq_times = nullptr, *wallq_stat = nullptr;
+  long wallq_cells_cap = 0, wallq_nodes_cap = 0, wallq_list_cap = 0;
+  size_t wallq_vals_cap = 0, wallq_times_cap = 0;
   FlowStats stats{};           // whole-field statistics (start_averaging)
   size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
   size_t stats_used = 0;       // of which the armed options use (stats_plane_count)

@@ -437,6 +437,7 @@ void DeviceSolver::upload() {
     static_assert(offsetof(StatsScalars, t_seen) + sizeof(double) == offsetof(StatsScalars, t_off), "adjacent");
     cp(&m.stats.sc->t_seen, st_clock, sizeof st_clock);
   }
+  if (wallq_armed) cp(&m.wallq.sc->s.t_seen, st_clock, sizeof st_clock);   // (the wall heat recorder's weights likewise)
   HIP_CHECK(hipStreamSynchronize(st));
   nstep = 0;
   abuf = 0;
@@ -445,6 +446,7 @@ void DeviceSolver::upload() {
   pbuf = 0;
   // (the records were replaced: the armed load recorder's cells follow their flags)
   if (loads_cap) loads_plan_rebuild();
+  if (wallq_armed) wallq_plan_upload(wallq_plan_build(wallq_opts));   // (and the wall heat recorder's nodes)
 }
 
 void DeviceSolver::set_lean_plain(bool on) {
@@ -532,6 +534,28 @@ void DeviceSolver::on_cycle_roll() {
     HIP_CHECK(hipStreamSynchronize(m.stream));
     for (double& t : tp) t -= T;
     HIP_CHECK(hipMemcpyAsync(m.loads.times, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+  }
+  if (wallq_armed) {
+    // the ring's times and the peak times (all set once a sample was taken), and the weights' clock offset
+    const size_t ne = (size_t)wallq_plan.nentries();
+    std::vector<double> tp((size_t)m.wallq.cap + ne);
+    WallHeatScalars ws;
+    if (m.wallq.cap)
+      HIP_CHECK(hipMemcpyAsync(tp.data(), m.wallq.times, (size_t)m.wallq.cap * sizeof(double), hipMemcpyDeviceToHost,
+                               m.stream));
+    HIP_CHECK(hipMemcpyAsync(tp.data() + m.wallq.cap, m.wallq.stat + 3 * ne, ne * sizeof(double), hipMemcpyDeviceToHost,
+                             m.stream));
+    HIP_CHECK(hipMemcpyAsync(&ws, m.wallq.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    for (double& t : tp) t -= T;
+    ws.s.t_off -= T;
+    if (m.wallq.cap)
+      HIP_CHECK(hipMemcpyAsync(m.wallq.times, tp.data(), (size_t)m.wallq.cap * sizeof(double), hipMemcpyHostToDevice,
+                               m.stream));
+    HIP_CHECK(hipMemcpyAsync(m.wallq.stat + 3 * ne, tp.data() + m.wallq.cap, ne * sizeof(double), hipMemcpyHostToDevice,
+                             m.stream));
+    HIP_CHECK(hipMemcpyAsync(&m.wallq.sc->s.t_off, &ws.s.t_off, sizeof(double), hipMemcpyHostToDevice, m.stream));
     HIP_CHECK(hipStreamSynchronize(m.stream));
   }
   if (stats_armed) {
@@ -658,7 +682,9 @@ uint64_t DeviceSolver::mode_signature() const {
                        // (likewise the accumulator's two launches: start / stop_averaging)
                        stats_gen,
                        // (and the load recorder's: record_loads, a plan rebuilt by upload)
-                       loads_gen};
+                       loads_gen,
+                       // (and the wall heat recorder's: record_wall_heat, a plan rebuilt by upload)
+                       wallq_gen};
   for (int f : state) mix(f);
   return h;
 }
@@ -843,6 +869,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   if (probe_cap) launch_probe_record(P);
   if (stats_on) launch_stats(P);
   if (loads_cap) launch_loads(P, c.slot, c.slot_next);
+  if (wallq_armed) launch_wall_heat(P, c.slot, c.slot_next);
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;
   StepResult r;
@@ -892,6 +919,8 @@ std::string DeviceSolver::autotune(int steps) {
   stats_on = false;
   const long s_loads = loads_cap;  // (nor the load recorder)
   loads_cap = 0;
+  const bool s_wallq = wallq_armed;   // (nor the wall heat recorder)
+  wallq_armed = false;
   struct Cand {
     int cpt, tj, nt, wgcu = 0;
   };
@@ -1023,6 +1052,7 @@ std::string DeviceSolver::autotune(int steps) {
   probe_cap = s_probe;
   stats_on = s_stats;
   loads_cap = s_loads;
+  wallq_armed = s_wallq;
   upload();   // device scalars from the restored host state
   graph_launches = 0;
   lns_steps = lnm_steps = 0;   // (the tuning steps do not count as the run's)

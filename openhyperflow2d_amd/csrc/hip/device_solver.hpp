@@ -124,6 +124,12 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void record_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) override;
   LoadHistory load_history() override;
   void clear_load_history() override;
+  // per-step wall heat recorder (hip/wall_heat.hpp): hf2d_wallq_tick,
+  // hf2d_wallq_cells and hf2d_wallq_fold follow the step while armed; reading
+  // the history neither leaves the lean state nor changes a ping-pong parity
+  void record_wall_heat(const WallHeatOpts& o) override;
+  WallHeatHistory wall_heat_history() override;
+  void clear_wall_heat() override;
   void trace_push(const char* name) override;
   void trace_pop() override;
   void synchronize();
@@ -262,6 +268,10 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   LoadPlan loads_plan;          // host copy of the armed plan
   std::vector<LoadBox> loads_boxes;
   std::vector<LoadCut> loads_cuts;
+  int wallq_gen = 0;            // arming generation (mode_signature, as probe_gen)
+  bool wallq_armed = false;
+  WallHeatOpts wallq_opts;      // what the plan is rebuilt from
+  WallHeatPlan wallq_plan;      // host copy of the armed plan
   bool fx_pending = false;   // fused tile steps left the newest ghost columns and dt in the mailbox (p2p_complete)
   // fused lean N-S steps: the last step's halo is still in the mailbox; the
   // next fused step's edge tiles unpack it (lns_ghost_prologue)
@@ -286,6 +296,10 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   LoadPlan loads_plan_build(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts) const;
   void loads_plan_upload(LoadPlan&& P);            // a built plan -> device
   void loads_plan_rebuild();                       // the armed boxes / cuts over the records upload() replaced
+  void launch_wall_heat(const StepParams& P, int slot, int slot_next);   // the wall heat recorder's three launches
+  WallHeatPlan wallq_plan_build(const WallHeatOpts& o) const;
+  void wallq_plan_upload(WallHeatPlan&& P);        // a built plan -> device
+  void wallq_reset();                              // ring and statistics empty, the clock at now
   void lns_fill_views(SoA& sin, SoA& out) const;   // the views lns_materialize's fill would run over now
   int post_step_view(SoA& s) const;                // PR_* kind and view both of them read
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)

@@ -1,10 +1,12 @@
 // Observers of the run: monitor points, the per-step probe recorder
-// (probe_history.hpp), the per-step load recorder (load_history.hpp) and the
-// time-averaged flow statistics (flow_stats.hpp).
+// (probe_history.hpp), the per-step load recorder (load_history.hpp), the
+// per-step wall heat recorder (wall_heat.hpp) and the time-averaged flow
+// statistics (flow_stats.hpp).
 
 #include "device_impl.hpp"
 #include "flow_stats.hpp"
 #include "load_history.hpp"
+#include "wall_heat.hpp"
 
 namespace hf2d {
 
@@ -384,6 +386,190 @@ void DeviceSolver::launch_loads(const StepParams& P, int slot, int slot_next) {
     HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(hf2d_loads_fold, dim3(1), dim3(LOADS_FOLD_WAVES * WAVE), 0, m.stream, L, m.sc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Per-step wall heat recorder (hip/wall_heat.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::record_wall_heat(const WallHeatOpts& o) {
+  check_record_wall_heat(o);   // (the options; one strip of several refuses)
+  Impl& m = *impl;
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  // (a refused plan throws here and leaves the armed recorder, if any, whole:
+  // its options, plan, ring and statistics are replaced only together, below)
+  WallHeatPlan P = wallq_plan_build(o);
+  const int cap = (int)std::min<long>(o.capacity, 0x7fffffffL);
+  const size_t ne = (size_t)P.nentries(), nv = (size_t)cap * ne;
+  WallHeatDev& L = m.wallq;
+  // (arrays that are large enough are used again: arming over and over does not grow device memory)
+  if (nv > m.wallq_vals_cap) {
+    m.wallq_vals = m.mem.alloc<real>(nv);
+    m.wallq_vals_cap = nv;
+  }
+  if ((size_t)cap > m.wallq_times_cap) {
+    m.wallq_times = m.mem.alloc<double>((size_t)cap);
+    m.wallq_times_cap = (size_t)cap;
+  }
+  if (!m.wallq_stat) m.wallq_stat = m.mem.alloc<double>(4 * ne);   // (nx, ny never change)
+  if (!L.sc) L.sc = m.mem.alloc<WallHeatScalars>(1);
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  wallq_armed = false;
+  wallq_plan_upload(std::move(P));
+  wallq_opts = o;
+  wallq_opts.capacity = cap;
+  L.vals = m.wallq_vals;
+  L.times = m.wallq_times;
+  L.stat = m.wallq_stat;
+  L.cap = cap;
+  L.statistics = o.statistics ? 1 : 0;
+  wallq_reset();
+  wallq_armed = true;
+}
+
+// The plan of the options over the records the backend holds now.  Throws
+// where a value could not be recorded exactly.
+WallHeatPlan DeviceSolver::wallq_plan_build(const WallHeatOpts& o) const {
+  WallHeatPlan P = build_wall_heat_plan(cs, cs.J, o, l_off);
+  for (long c : P.cells)
+    if (c < 0 || c >= h.N) throw std::runtime_error("wall heat recorder: a needed cell lies outside the solver's arrays");
+  // the lean N-S / mechanism kinds fill a needed cell with the parameters of
+  // the recorded step; the fill a download runs takes the next step's, whose
+  // is_mu_t differs after the last step before TurbStartIter (the load
+  // recorder's refusal, loads_plan_build, and its reasoning)
+  if (P.nnodes() > 0 && (lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset &&
+      cs.cfg.TurbStartIter >= 2 && last_iter + iter < (long)cs.cfg.TurbStartIter)
+    throw std::runtime_error("wall heat recorder: wall nodes on the lean N-S / mechanism state cannot be recorded "
+                             "exactly before TurbStartIter has passed; arm (or upload) later");
+  // a plain lean tile step stores no T, and T = p / R / rho holds only where R
+  // does not change over the step; the tile kernel runs its output variant for
+  // the probe recorder and the accumulator alone (step_tile.hip)
+  if (P.nnodes() > 0 && lean_ok && !lean_sg_ok && make_params(last_iter + iter).chem_model != NO_REACTIONS)
+    throw std::runtime_error("wall heat recorder: a reacting gas mixture on the lean inviscid step stores no wall "
+                             "temperature between outputs; the recorder cannot be armed on this deck");
+  return P;
+}
+
+// A built plan into the device arrays (used again where they are large
+// enough; the stream is idle: flush_pending / upload synchronised it).
+void DeviceSolver::wallq_plan_upload(WallHeatPlan&& P) {
+  Impl& m = *impl;
+  const long nc = P.ncells(), nn = P.nnodes(), nl = (long)P.list.size();
+  const int no = P.nlists() + 1;
+  if (nc > m.wallq_cells_cap) {
+    m.wallq_cells = m.mem.alloc<long>((size_t)nc);
+    m.wallq_scratch = m.mem.alloc<real>(3 * (size_t)nc);
+    m.wallq_cells_cap = nc;
+  }
+  if (nn > m.wallq_nodes_cap) {
+    m.wallq_node5 = m.mem.alloc<int>(5 * (size_t)nn);
+    m.wallq_nodes_cap = nn;
+  }
+  if (nl > m.wallq_list_cap) {
+    m.wallq_list = m.mem.alloc<int>((size_t)nl);
+    m.wallq_list_cap = nl;
+  }
+  if (!m.wallq_off) m.wallq_off = m.mem.alloc<int>((size_t)no);   // (nx + ny + 1: never changes)
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets, and nothing in flight reads the arrays)
+  auto cp = [&](void* d, const void* s, size_t bytes) {
+    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, m.stream));
+  };
+  cp(m.wallq_cells, P.cells.data(), nc * sizeof(long));
+  cp(m.wallq_node5, P.node5.data(), 5 * nn * sizeof(int));
+  cp(m.wallq_list, P.list.data(), nl * sizeof(int));
+  cp(m.wallq_off, P.off.data(), (size_t)no * sizeof(int));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  WallHeatDev& L = m.wallq;
+  L.K = P.K;
+  L.cells = m.wallq_cells;
+  L.node5 = m.wallq_node5;
+  L.list = m.wallq_list;
+  L.off = m.wallq_off;
+  L.scratch = m.wallq_scratch;
+  L.ncells = nc;
+  L.nx = P.nx;
+  L.ny = P.ny;
+  wallq_plan = std::move(P);
+  wallq_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+// An empty ring and empty statistics whose clock starts at the present value.
+void DeviceSolver::wallq_reset() {
+  Impl& m = *impl;
+  WallHeatScalars s0{};
+  s0.s.every = wallq_opts.every;
+  s0.s.step_weight = wallq_opts.step_weight ? 1 : 0;
+  s0.s.t_off = time_offset;
+  HIP_CHECK(hipMemcpyAsync(m.wallq.sc, &s0, sizeof s0, hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipMemsetAsync(m.wallq.stat, 0, 4 * (size_t)wallq_plan.nentries() * sizeof(double), m.stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, &m.wallq.sc->s, m.sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+void DeviceSolver::clear_wall_heat() {
+  if (!wallq_armed) return;
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  wallq_reset();
+}
+
+WallHeatHistory DeviceSolver::wall_heat_history() {
+  if (!wallq_armed) throw std::runtime_error("wall_heat_history: no recorder armed (record_wall_heat)");
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const WallHeatDev& L = m.wallq;
+  const size_t ne = (size_t)wallq_plan.nentries();
+  WallHeatScalars ws;
+  std::vector<real> vals((size_t)L.cap * ne);
+  std::vector<double> tp((size_t)L.cap), stat(4 * ne);
+  HIP_CHECK(hipMemcpyAsync(&ws, L.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
+  if (!vals.empty()) {
+    HIP_CHECK(hipMemcpyAsync(vals.data(), L.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+    HIP_CHECK(hipMemcpyAsync(tp.data(), L.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  }
+  HIP_CHECK(hipMemcpyAsync(stat.data(), L.stat, stat.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  // (the probe ring's clock: probe_history)
+  return wall_heat_history_from(wallq_plan, wallq_opts, vals.data(), tp.data(), (long)ws.s.samples, stat.data(), ws.s,
+                                [&](double t) {
+                                  const real part = t - time_offset;
+                                  return (double)(cs.global_time + part);
+                                });
+}
+
+// After the other observers' launches; the same view, and for the lean N-S /
+// mechanism state the materialise fill's (as launch_loads).  Nothing here
+// allocates, copies or synchronises.
+void DeviceSolver::launch_wall_heat(const StepParams& P, int slot, int slot_next) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
+  SoA fin = s, out = s;
+  // the dt slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3, else (nstep + 2) % 3)
+  int fslot = slot;
+  if (lns_state) {
+    lns_fill_views(fin, out);
+    if (kind == PR_SGL) fslot = slot_next;
+  }
+  const WallHeatDev& L = m.wallq;
+  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.sc, m.sc, L.cap);
+  HIP_CHECK(hipGetLastError());
+  if (L.ncells > 0) {
+    const dim3 g((unsigned)((L.ncells + WALLQ_BLOCK - 1) / WALLQ_BLOCK)), b(WALLQ_BLOCK);
+    switch (kind) {
+      case PR_SGL: hipLaunchKernelGGL(hf2d_wallq_cells<PR_SGL>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_SGT: hipLaunchKernelGGL(hf2d_wallq_cells<PR_SGT>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_MECH: hipLaunchKernelGGL(hf2d_wallq_cells<PR_MECH>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_LEAN: hipLaunchKernelGGL(hf2d_wallq_cells<PR_LEAN>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      default: hipLaunchKernelGGL(hf2d_wallq_cells<PR_GATHER>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(hf2d_wallq_fold, dim3((unsigned)(L.nx + L.ny)), dim3(WALLQ_BLOCK), 0, m.stream, L, m.sc);
   HIP_CHECK(hipGetLastError());
 }
 

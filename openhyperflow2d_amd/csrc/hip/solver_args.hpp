@@ -5,6 +5,7 @@
 #pragma once
 
 #include "../core/lean_euler.hpp"
+#include "../core/wall_heat.hpp"
 
 namespace hf2d {
 
@@ -109,6 +110,28 @@ struct LoadsDev {
   real* vals = nullptr;        // [cap][nlists]
   double* times = nullptr;     // [cap] DevScalars::time_part after the step
   unsigned long long* count = nullptr;   // rows written since arming
+};
+
+// Per-step wall heat recorder (wall_heat.hpp): what its tick leaves for the
+// two kernels behind it, the plan, the ring and the statistics
+struct WallHeatScalars {
+  StatsScalars s;   // the sampling decision and the weights (stats_tick)
+  long slot = 0;    // ring row of this sample
+};
+struct WallHeatDev {
+  WallHeatConst K;
+  // the plan (WallHeatPlan)
+  const long* cells = nullptr;   // [ncells]
+  const int* node5 = nullptr;    // [nnodes][5]
+  const int* off = nullptr;      // [nx + ny + 1]
+  const int* list = nullptr;
+  long ncells = 0;
+  int nx = 0, ny = 0, cap = 0, statistics = 0;
+  real* scratch = nullptr;       // [3][ncells] lam + lam_t, Tg, p of the needed cells after the step
+  real* vals = nullptr;          // [cap][4 nx + ny]
+  double* times = nullptr;       // [cap] DevScalars::time_part after the step
+  double* stat = nullptr;        // [4][4 nx + ny] m, M, peak, peak_time (DevScalars::time_part)
+  WallHeatScalars* sc = nullptr;
 };
 
 }  // namespace hf2d

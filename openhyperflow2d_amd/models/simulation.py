@@ -46,6 +46,7 @@ def parse_fault(spec: str):
 
 PROBE_VARS = ("p", "T", "rho", "U", "V")   # column order of Simulation.probe_history()["values"]
 LOAD_PARTS = ("Fx_p", "Fx_d", "Fy_p", "Fy_d")   # last axis of Simulation.load_history()["forces"]
+WALL_HEAT_X = ("Q", "Alpha", "Cp", "St")   # rows of Case.heat_flux_x() and of Simulation.wall_heat_history()["x"]
 
 
 class Simulation:
@@ -182,6 +183,56 @@ class Simulation:
     def clear_load_history(self) -> None:
         """Drop the recorded rows; the recorder stays armed on the same boxes and cuts."""
         self.solver.clear_load_history()
+
+    # -- per-step wall heat recorder ------------------------------------------
+    def record_wall_heat(self, x: bool = True, y: bool = True, cp_flow=None, rows=None, every: int = 1,
+                         capacity: int = 1024, statistics: bool = True, weight: str = "time") -> None:
+        """Arm the per-step wall heat recorder: the ``HeatFlux-X`` profile
+        (``WALL_HEAT_X = ("Q", "Alpha", "Cp", "St")`` per column) when ``x``
+        and the ``HeatFlux-Y`` profile (``Q`` per row) when ``y``.
+
+        From now on every ``every``-th step appends both profiles and the
+        step's time to a ring of ``capacity`` rows kept by the backend
+        (``capacity=0``: statistics only), and with ``statistics`` folds every
+        profile entry into a running mean, variance, peak and peak time
+        (``weight``: ``"time"``, the span since the previous sample, or
+        ``"step"``).  Every value is bit for bit ``case.heat_flux_x(cp_flow,
+        rows)`` / ``case.heat_flux_y()`` on a field downloaded after that
+        step.  ``cp_flow`` (1-based) and ``rows = (y_min, y_max)`` default to
+        the deck's ``Cp_Flow_Index``, ``y_min`` and ``y_max``.  A profile that
+        is not requested reads ``+0.0`` with node counts 0.  On the GPU up to
+        three small kernels run at the end of each step, inside the step
+        graphs, and the lean states are never materialised.  Arming again
+        replaces the recorder.  ``ValueError``: neither profile, ``every <
+        1``, ``capacity < 0``, an unknown ``weight``, or ``x`` with a flow
+        index the case does not have.  ``RuntimeError``: the solver is one
+        strip of several (a one-process run only), or the values could not
+        be recorded exactly yet (see the README)."""
+        if weight not in ("time", "step"):
+            raise ValueError("record_wall_heat: weight is 'time' or 'step', not %r" % (weight,))
+        keys = self.case.wall_heat_keys
+        f = int(keys["Cp_Flow_Index"] if cp_flow is None else cp_flow)
+        y0, y1 = (keys["y_min"], keys["y_max"]) if rows is None else rows
+        self.solver.record_wall_heat(bool(x), bool(y), f, int(y0), int(y1), int(every), int(capacity),
+                                     bool(statistics), weight == "step")
+
+    def wall_heat_history(self) -> dict:
+        """The recorded samples, oldest first: ``times`` [n] (the clock of
+        ``probe_history()``), ``x`` [n, 4, nx] in ``WALL_HEAT_X`` order, ``y``
+        [n, ny], ``total`` (samples taken since arming; n = min(total,
+        capacity)), ``x_nodes`` [nx] and ``y_nodes`` [ny] (the static number
+        of wall nodes of every column and row), and with statistics
+        ``mean_x``, ``var_x``, ``peak_x``, ``peak_time_x`` [4, nx], the same
+        four ``_y`` keys [ny], ``time`` (the weight sum) and ``samples``.
+        Reading does not disturb the solver state."""
+        h = dict(self.solver.wall_heat_history())
+        for k, v in h.items():
+            h[k] = int(v) if k in ("total", "samples") else float(v) if k == "time" else np.asarray(v)
+        return h
+
+    def clear_wall_heat(self) -> None:
+        """Empty the ring and the statistics; the recorder stays armed."""
+        self.solver.clear_wall_heat()
 
     # -- time-averaged flow statistics ---------------------------------------
     def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time",
