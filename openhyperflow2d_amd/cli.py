@@ -8,6 +8,7 @@
                                      [--probe-history FILE.npz [--probe-capacity N]]
                                      [--load-history FILE.npz [--load-capacity N]]
                                      [--wall-heat FILE.npz [--wall-heat-every K] [--wall-heat-capacity N]]
+                                     [--surface FILE.npz [--surface-every K] [--surface-capacity N]]
                                      [--averages FILE.npz [--averages-every K] [--averages-favre]
                                       [--averages-species all|A,B,...]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
@@ -56,6 +57,11 @@ def _cmd_run(a) -> int:
     if a.wall_heat and world > 1:
         if rank == 0:
             print("--wall-heat records in one process only; this is a %d-rank launch "
+                  "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
+        return 2
+    if a.surface and world > 1:
+        if rank == 0:
+            print("--surface records in one process only; this is a %d-rank launch "
                   "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
         return 2
     if a.averages and world > 1:
@@ -115,6 +121,16 @@ def _cmd_run(a) -> int:
         except (ValueError, RuntimeError) as e:
             print("--wall-heat: %s" % e, file=sys.stderr, flush=True)
             return 2
+    if a.surface:
+        # the nodes of the deck's body box (is_Cx_calc), else every node; the deck's Cp flow where it names one
+        boxes = sim.case.load_targets[0] or None
+        keys = sim.case.wall_heat_keys
+        flow = keys["Cp_Flow_Index"] if 1 <= keys["Cp_Flow_Index"] <= keys["flows"] else 1
+        try:
+            sim.record_surface(boxes=boxes, cp_flow=flow, every=a.surface_every, capacity=a.surface_capacity)
+        except (ValueError, RuntimeError) as e:
+            print("--surface: %s" % e, file=sys.stderr, flush=True)
+            return 2
     if a.averages:
         try:
             sp = a.averages_species
@@ -167,6 +183,16 @@ def _cmd_run(a) -> int:
         print("wall heat: %d of %d samples x (4 x %d + %d) entries -> %s" % (h["times"].shape[0], h["total"],
                                                                             h["x"].shape[2], h["y"].shape[1],
                                                                             a.wall_heat), flush=True)
+    if a.surface:
+        import numpy as np
+
+        from .models.simulation import SURFACE_VARS
+
+        h = sim.surface_history()
+        with open(a.surface, "wb") as f:   # (np.savez on a path would append ".npz")
+            np.savez(f, vars=np.asarray(SURFACE_VARS), **{k: np.asarray(v) for k, v in h.items()})
+        print("surface: %d of %d samples x 10 x %d nodes -> %s" % (h["times"].shape[0], h["total"],
+                                                                   h["values"].shape[2], a.surface), flush=True)
     if a.averages:
         import numpy as np
 
@@ -289,6 +315,15 @@ def main(argv=None) -> int:
                    help="sample every K-th step (default 1)")
     r.add_argument("--wall-heat-capacity", dest="wall_heat_capacity", type=int, default=4096, metavar="N",
                    help="rows the wall heat recorder keeps: the last N samples (default 4096; 0: statistics only)")
+    r.add_argument("--surface", metavar="FILE.npz",
+                   help="record p, Cp, T, tau_x, tau_y, Cf_x, Cf_y, q_y, q_x, St of every wall node of the deck's body "
+                        "box (is_Cx_calc; else of the whole field) after every K-th step (one process only) and write "
+                        "times / values / total, the node table (i, j, x, y, flags, face_x, face_y, fric_x, fric_y, "
+                        "box_off), the running mean / var / peak / peak_time, time, samples and vars to this file")
+    r.add_argument("--surface-every", dest="surface_every", type=int, default=1, metavar="K",
+                   help="sample every K-th step (default 1)")
+    r.add_argument("--surface-capacity", dest="surface_capacity", type=int, default=4096, metavar="N",
+                   help="rows the surface recorder keeps: the last N samples (default 4096; 0: statistics only)")
     r.add_argument("--averages", metavar="FILE.npz",
                    help="accumulate time-averaged p, T, rho, U, V, their variances and the U-V covariance over the "
                         "whole field at every step (one process only) and write mean / var / cov_uv / vars / time / "

@@ -134,6 +134,36 @@ void bind_solver_common(py::class_<T, SolverBase>& c) {}
 
 }  // namespace
 
+// The static node table of a surface plan into a dict (Case.surface, surface_history)
+static void surface_table(py::dict& d, const hf2d::SurfacePlan& P) {
+  using namespace hf2d;
+  const py::ssize_t nn = (py::ssize_t)P.nnodes();
+  auto put = [&](const char* k, const auto& v, auto tag) {
+    py::array_t<decltype(tag)> a(std::vector<py::ssize_t>{(py::ssize_t)v.size()});
+    std::copy(v.begin(), v.end(), a.mutable_data());
+    d[k] = a;
+  };
+  put("i", P.ni, int{});
+  put("j", P.nj, int{});
+  put("x", P.x, real{});
+  put("y", P.y, real{});
+  std::vector<int> fl(nn);
+  for (py::ssize_t n = 0; n < nn; n++) fl[n] = P.bits[n] & (SN_NO_SLIP | SN_LAW | SN_SOLID_NB);
+  put("flags", fl, int{});
+  put("face_x", P.face_x, real{});
+  put("face_y", P.face_y, real{});
+  put("fric_x", P.fric_x, real{});
+  put("fric_y", P.fric_y, real{});
+  put("box_off", P.box_off, long{});
+}
+static hf2d::SurfaceOpts surface_opts(py::object boxes, int cp_flow) {
+  hf2d::SurfaceOpts o;
+  o.all = boxes.is_none();
+  if (!o.all) o.boxes = boxes.cast<std::vector<hf2d::LoadBox>>();
+  o.cp_flow = cp_flow;
+  return o;
+}
+
 PYBIND11_MODULE(_hf2d, m) {
   m.doc() = "hf2d native runtime: OpenHyperFLOW2D-compatible DEEPS solver for AMD MI355X";
   m.attr("CELL_RECORD_BYTES") = (int)sizeof(CellRecord);
@@ -611,7 +641,28 @@ PYBIND11_MODULE(_hf2d, m) {
         py::array_t<real> a(std::vector<py::ssize_t>{(py::ssize_t)c.J.ny});
         std::copy(Q.begin(), Q.end(), a.mutable_data());
         return a;
-      }, "[ny] the HeatFlux-Y profile of the records (heat_flux_y_terms, fold_heat_flux_y)");
+      }, "[ny] the HeatFlux-Y profile of the records (heat_flux_y_terms, fold_heat_flux_y)")
+      .def("surface",
+           [](const Case& c, py::object boxes, py::object cp_flow) {
+             // the node table and the ten values of every node of the records (surface_plan.hpp)
+             need_whole(c);
+             SurfaceOpts o = surface_opts(boxes, cp_flow.is_none() ? c.cfg.Cp_Flow_index : cp_flow.cast<int>());
+             const SurfacePlan P = build_surface_plan(c, c.J, o);
+             std::vector<real> sc((size_t)SURFACE_PLANES * P.ncells());
+             surface_scratch_of_records(P, c.J, 0, sc.data());
+             const py::ssize_t nn = (py::ssize_t)P.nnodes();
+             py::array_t<real> v(std::vector<py::ssize_t>{(py::ssize_t)SURFACE_NVARS, nn});
+             StatsScalars tk;
+             surface_sample(P, sc.data(), v.mutable_data(), nullptr, tk, 0.0);
+             py::dict d;
+             surface_table(d, P);
+             d["values"] = v;
+             return d;
+           },
+           py::arg("boxes") = py::none(), py::arg("cp_flow") = py::none(),
+           "the wall nodes of the records (every node, or those of each box (x0, y0, dx, dy) in turn): i, j, x, y, "
+           "flags, face_x, face_y, fric_x, fric_y, box_off and values [10, nnodes] in SURFACE_VARS order; cp_flow: "
+           "1-based flow index (default: the deck's Cp_Flow_Index)");
 
   m.def(
       "lean_tile_geom",
@@ -829,6 +880,50 @@ PYBIND11_MODULE(_hf2d, m) {
              return d;
            })
       .def("clear_wall_heat", &SolverBase::clear_wall_heat)
+      .def("record_surface",
+           [](SolverBase& s, py::object boxes, int cp_flow, int every, long capacity, bool statistics, bool step_weight) {
+             SurfaceOpts o = surface_opts(boxes, cp_flow);
+             o.every = every;
+             o.capacity = capacity;
+             o.statistics = statistics;
+             o.step_weight = step_weight;
+             s.record_surface(o);
+           },
+           py::arg("boxes"), py::arg("cp_flow"), py::arg("every") = 1, py::arg("capacity") = 1024,
+           py::arg("statistics") = true, py::arg("step_weight") = false,
+           "arm the per-step surface recorder: p, Cp, T, tau_x, tau_y, Cf_x, Cf_y, q_y, q_x, St of every wall node "
+           "(of each box in turn, or of the whole field with boxes=None) after every `every`-th step")
+      .def("surface_history",
+           [](SolverBase& s) {
+             SurfaceHistory H;
+             {
+               py::gil_scoped_release rel;
+               H = s.surface_history();
+             }
+             const py::ssize_t n = (py::ssize_t)H.times.size(), nn = (py::ssize_t)H.nnodes, nv = SURFACE_NVARS;
+             py::array_t<double> t(std::vector<py::ssize_t>{n});
+             py::array_t<real> v(std::vector<py::ssize_t>{n, nv, nn});
+             std::copy(H.times.begin(), H.times.end(), t.mutable_data());
+             std::copy(H.vals.begin(), H.vals.end(), v.mutable_data());
+             py::dict d;
+             d["times"] = t;
+             d["values"] = v;
+             d["total"] = H.total;
+             surface_table(d, s.surface_plan());
+             if (H.statistics) {
+               const char* names[4] = {"mean", "var", "peak", "peak_time"};
+               const std::vector<double>* src[4] = {&H.mean, &H.var, &H.peak, &H.peak_time};
+               for (int q = 0; q < 4; q++) {
+                 py::array_t<double> a(std::vector<py::ssize_t>{nv, nn});
+                 std::copy(src[q]->begin(), src[q]->end(), a.mutable_data());
+                 d[names[q]] = a;
+               }
+               d["time"] = H.time;
+               d["samples"] = H.samples;
+             }
+             return d;
+           })
+      .def("clear_surface", &SolverBase::clear_surface)
       .def("start_averaging", &SolverBase::start_averaging, py::arg("every") = 1, py::arg("second_moments") = true,
            py::arg("step_weight") = false, py::arg("favre") = false, py::arg("species") = std::vector<int>{},
            "arm the whole-field accumulator: weighted running mean (and variances, U-V covariance) of "

@@ -77,6 +77,76 @@ HF_HD inline real load_term(int kind, real coef, real a, real mu, real mu_t, rea
   return nb > 0 ? tau : -tau;
 }
 
+// A wall node's part in the four force lists of a box: the signed areas of its
+// pressure terms (-Sp or Sp; +0.0: none), the coefficients of its friction
+// terms (Sd, -Sd; +0.0: none) and the neighbour whose U / V gives each friction
+// term its sign, as x_force_terms / y_force_terms choose them.  The load plan
+// and the surface plan (surface_plan.hpp) both call this.
+struct WallNodeTerms {
+  real face_x = 0, face_y = 0, fric_x = 0, fric_y = 0;
+  bool has_px = false, has_py = false, has_fx = false, has_fy = false;
+  int fx_i = 0, fx_j = 0, fy_i = 0, fy_j = 0;
+};
+inline WallNodeTerms wall_node_terms(const Config& C, const Field& J, int i, int j) {
+  WallNodeTerms t;
+  const CellRecord& n = J.at(i, j);
+  {   // x_force_terms
+    real Sp, Sd;
+    if (C.FT == FT_FLAT) {
+      Sp = C.dy;
+      Sd = C.dx;
+    } else {
+      Sp = 2 * M_PI * (j + 0.5) * C.dy * C.dy;
+      Sd = 2 * M_PI * (j + 0.5) * C.dy * C.dx;
+    }
+    if (i > 0 && J.at(i - 1, j).is(CT_SOLID)) {
+      t.has_px = true;
+      t.face_x = -Sp;
+    } else if (i < J.nx - 1 && J.at(i + 1, j).is(CT_SOLID)) {
+      t.has_px = true;
+      t.face_x = Sp;
+    }
+    if (j < J.ny - 1 && !J.at(i, j + 1).is(CT_SOLID)) {
+      t.has_fx = true;
+      t.fx_i = i;
+      t.fx_j = j + 1;
+    } else if (j > 0 && !J.at(i, j - 1).is(CT_SOLID)) {
+      t.has_fx = true;
+      t.fx_i = i;
+      t.fx_j = j - 1;
+    }
+    if (t.has_fx) t.fric_x = Sd;
+  }
+  {   // y_force_terms
+    real Sp, Sd;
+    if (C.FT == FT_FLAT) {
+      Sp = C.dx;
+      Sd = C.dy;
+    } else {
+      Sp = 2 * M_PI * n.y * C.dx;
+      Sd = 2 * M_PI * n.y * C.dy;
+    }
+    if (j > 0 && J.at(i, j - 1).is(CT_SOLID)) {
+      t.has_py = true;
+      t.face_y = -Sp;
+    } else if (j < J.ny - 1 && J.at(i, j + 1).is(CT_SOLID)) {
+      t.has_py = true;
+      t.face_y = Sp;
+    }
+    if (i < J.nx - 1 && !J.at(i + 1, j).is(CT_SOLID)) {
+      t.has_fy = true;
+      t.fy_i = i + 1;
+      t.fy_j = j;
+    } else if (i > 0 && !J.at(i - 1, j).is(CT_SOLID)) {
+      t.has_fy = true;
+      t.fy_i = i - 1;
+      t.fy_j = j;
+    }
+    if (t.has_fy) t.fric_y = -Sd;
+  }
+  return t;
+}
+
 inline void check_loads(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts, long capacity) {
   if (boxes.empty() && cuts.empty()) throw std::invalid_argument("record_loads: no box and no cut");
   if ((int)boxes.size() > LOAD_MAX)
@@ -115,58 +185,16 @@ inline LoadPlan build_load_plan(const Case& cs, const Field& J, const std::vecto
   };
   L.off.push_back(0);
   for (const LoadBox& b : boxes) {
-    // x_force_terms: fp, then fd
-    for (int part = 0; part < 2; part++) {
+    // x_force_terms: fp, then fd; y_force_terms: fp, then fd
+    for (int part = 0; part < LOAD_PARTS; part++) {
       for (int i = 0; i < J.nx; i++)
         for (int j = 0; j < J.ny; j++) {
           if (!wall_in(i, j, b)) continue;
-          real Sp, Sd;
-          if (C.FT == FT_FLAT) {
-            Sp = C.dy;
-            Sd = C.dx;
-          } else {
-            Sp = 2 * M_PI * (j + 0.5) * C.dy * C.dy;
-            Sd = 2 * M_PI * (j + 0.5) * C.dy * C.dx;
-          }
-          if (part == 0) {
-            if (i > 0 && J.at(i - 1, j).is(CT_SOLID))
-              push(LK_P, at(i, j), at(i, j), -Sp);
-            else if (i < J.nx - 1 && J.at(i + 1, j).is(CT_SOLID))
-              push(LK_P, at(i, j), at(i, j), Sp);
-          } else {
-            if (j < J.ny - 1 && !J.at(i, j + 1).is(CT_SOLID))
-              push(LK_FX, at(i, j), at(i, j + 1), Sd);
-            else if (j > 0 && !J.at(i, j - 1).is(CT_SOLID))
-              push(LK_FX, at(i, j), at(i, j - 1), Sd);
-          }
-        }
-      L.off.push_back(L.nterms());
-    }
-    // y_force_terms: fp, then fd
-    for (int part = 0; part < 2; part++) {
-      for (int i = 0; i < J.nx; i++)
-        for (int j = 0; j < J.ny; j++) {
-          if (!wall_in(i, j, b)) continue;
-          const CellRecord& n = J.at(i, j);
-          real Sp, Sd;
-          if (C.FT == FT_FLAT) {
-            Sp = C.dx;
-            Sd = C.dy;
-          } else {
-            Sp = 2 * M_PI * n.y * C.dx;
-            Sd = 2 * M_PI * n.y * C.dy;
-          }
-          if (part == 0) {
-            if (j > 0 && J.at(i, j - 1).is(CT_SOLID))
-              push(LK_P, at(i, j), at(i, j), -Sp);
-            else if (j < J.ny - 1 && J.at(i, j + 1).is(CT_SOLID))
-              push(LK_P, at(i, j), at(i, j), Sp);
-          } else {
-            if (i < J.nx - 1 && !J.at(i + 1, j).is(CT_SOLID))
-              push(LK_FY, at(i, j), at(i + 1, j), -Sd);
-            else if (i > 0 && !J.at(i - 1, j).is(CT_SOLID))
-              push(LK_FY, at(i, j), at(i - 1, j), -Sd);
-          }
+          const WallNodeTerms t = wall_node_terms(C, J, i, j);
+          if (part == 0 && t.has_px) push(LK_P, at(i, j), at(i, j), t.face_x);
+          if (part == 1 && t.has_fx) push(LK_FX, at(i, j), at(t.fx_i, t.fx_j), t.fric_x);
+          if (part == 2 && t.has_py) push(LK_P, at(i, j), at(i, j), t.face_y);
+          if (part == 3 && t.has_fy) push(LK_FY, at(i, j), at(t.fy_i, t.fy_j), t.fric_y);
         }
       L.off.push_back(L.nterms());
     }

@@ -480,6 +480,22 @@ WallHeatHistory SolverBase::wall_heat_history() {
 }
 void SolverBase::clear_wall_heat() {}
 
+void SolverBase::check_record_surface(const SurfaceOpts& o) const {
+  check_surface(o);
+  const auto own = owned_columns();
+  if (comm->size() > 1 || own.first != 0 || own.second != cs.J.nx || !cs.J.whole())
+    throw std::runtime_error("record_surface: this solver is one strip of several; the per-step surface recorder "
+                             "needs a one-process run (the node lists run over the whole field)");
+}
+void SolverBase::record_surface(const SurfaceOpts&) {
+  throw std::runtime_error("this backend has no per-step surface recorder");
+}
+SurfaceHistory SolverBase::surface_history() { throw std::runtime_error("this backend has no per-step surface recorder"); }
+const SurfacePlan& SolverBase::surface_plan() const {
+  throw std::runtime_error("this backend has no per-step surface recorder");
+}
+void SolverBase::clear_surface() {}
+
 void SolverBase::start_averaging(int, bool, bool, bool, const std::vector<int>&) {
   throw std::runtime_error("this backend has no flow-statistics accumulator");
 }
@@ -988,6 +1004,7 @@ void CpuSolver::after_step() {
   }
   if (load_cap) record_loads_step();
   if (wq_armed) record_wall_heat_step();
+  if (sf_armed) record_surface_step();
   if (probe_cap == 0) return;
   const size_t np = probe_idx.size();
   const long slot = probe_total % probe_cap;
@@ -1091,6 +1108,82 @@ WallHeatHistory CpuSolver::wall_heat_history() {
                                 [](double t) { return t; });
 }
 
+void CpuSolver::record_surface(const SurfaceOpts& o) {
+  check_record_surface(o);
+  // (a refused plan throws here and leaves the armed recorder, if any, whole)
+  SurfacePlan P = build_surface_plan(cs, cs.J, o, l_off);
+  sf_plan = std::move(P);
+  sf_opts = o;
+  sf_vals.assign((size_t)o.capacity * SURFACE_NVARS * sf_plan.nnodes(), 0.0);
+  sf_times.assign((size_t)o.capacity, 0.0);
+  sf_scratch.assign((size_t)SURFACE_PLANES * sf_plan.ncells(), 0.0);
+  sf_armed = true;
+  clear_surface();
+}
+
+// the ring and the statistics restart; the sampling count and the clock with them
+void CpuSolver::clear_surface() {
+  if (!sf_armed) return;
+  sf_total = 0;
+  sf_sc = StatsScalars{};
+  sf_sc.every = sf_opts.every;
+  sf_sc.step_weight = sf_opts.step_weight ? 1 : 0;
+  sf_sc.t_seen = (double)(cs.global_time + cur_time_part);
+  sf_stat.assign(4 * (size_t)SURFACE_NVARS * sf_plan.nnodes(), 0.0);
+}
+
+// the needed cells from the arrays download() would copy, then every node's ten values
+void CpuSolver::record_surface_step() {
+  const double t = (double)(cs.global_time + cur_time_part);
+  if (!stats_tick(sf_sc, t)) return;
+  const SurfacePlan& L = sf_plan;
+  const size_t nc = (size_t)L.ncells(), ne = (size_t)SURFACE_NVARS * L.nnodes();
+  const real* p = lean_state ? P2[pbuf].data() : h.p.data();
+  const real* gU = h.grad.data() + (size_t)G_DUDY * h.N;
+  const real* gV = h.grad.data() + (size_t)G_DVDX * h.N;
+  real* sc = sf_scratch.data();
+  for (size_t k = 0; k < nc; k++) {
+    const long c = L.cells[k];
+    sc[SP_P * nc + k] = p[c];
+    sc[SP_T * nc + k] = h.Tg[pbuf][c];
+    sc[SP_SL * nc + k] = h.lam[c] + h.lam_t[c];
+    sc[SP_MU * nc + k] = h.mu[c];
+    sc[SP_MUT * nc + k] = h.mu_t[c];
+    sc[SP_DUDY * nc + k] = gU[c];
+    sc[SP_DVDX * nc + k] = gV[c];
+    sc[SP_U * nc + k] = h.U[pbuf][c];
+    sc[SP_V * nc + k] = h.V[pbuf][c];
+  }
+  const long cap = sf_opts.capacity;
+  const long slot = cap ? sf_total % cap : 0;
+  surface_sample(L, sc, cap ? sf_vals.data() + (size_t)slot * ne : nullptr,
+                 sf_opts.statistics ? sf_stat.data() : nullptr, sf_sc, t);
+  if (cap) sf_times[slot] = t;
+  sf_total++;
+}
+
+// upload() replaced the records: the same options over the new flags.  The
+// ring and the statistics keep their rows while the node count stays; with
+// another count they restart, as after arming.
+void CpuSolver::sf_rebuild() {
+  const long nn = sf_plan.nnodes();
+  sf_plan = build_surface_plan(cs, cs.J, sf_opts, l_off);
+  sf_scratch.assign((size_t)SURFACE_PLANES * sf_plan.ncells(), 0.0);
+  if (sf_plan.nnodes() == nn) return;
+  sf_vals.assign((size_t)sf_opts.capacity * SURFACE_NVARS * sf_plan.nnodes(), 0.0);
+  clear_surface();
+}
+
+SurfaceHistory CpuSolver::surface_history() {
+  if (!sf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
+  return surface_history_from(sf_plan, sf_opts, sf_vals.data(), sf_times.data(), sf_total, sf_stat.data(), sf_sc,
+                              [](double t) { return t; });
+}
+const SurfacePlan& CpuSolver::surface_plan() const {
+  if (!sf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
+  return sf_plan;
+}
+
 ProbeHistory CpuSolver::probe_history() {
   if (probe_cap == 0) throw std::runtime_error("probe_history: no recorder armed (record_probes)");
   ProbeHistory H;
@@ -1129,6 +1222,7 @@ void CpuSolver::upload() {
     wq_plan = build_wall_heat_plan(cs, cs.J, wq_opts, l_off);
     wq_scratch.assign(3 * (size_t)wq_plan.ncells(), 0.0);
   }
+  if (sf_armed) sf_rebuild();   // (and the surface recorder's)
   if (lean_ok) {
     lb = lean_flags(h, cs.cfg.ProblemType);
     for (int b = 0; b < 2; b++) {

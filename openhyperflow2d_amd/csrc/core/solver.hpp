@@ -24,6 +24,7 @@
 #include "flow_stats.hpp"
 #include "load_plan.hpp"
 #include "wall_heat.hpp"
+#include "surface_plan.hpp"
 
 namespace hf2d {
 
@@ -276,6 +277,23 @@ class SolverBase {
   // record_wall_heat's checks: the options, and that this solver holds the whole field
   void check_record_wall_heat(const WallHeatOpts& o) const;
 
+  // Opt-in per-step surface recorder (core/surface_plan.hpp): after every
+  // `every`-th step the ten values (p, Cp, T, tau_x, tau_y, Cf_x, Cf_y, q_y,
+  // q_x, St) of every listed wall node, bit for bit what surface_values gives
+  // on a field downloaded after that step, and the step's time go into a ring
+  // of `capacity` rows (0: none), and with `statistics` into a running mean,
+  // variance, peak and peak time per entry.  Arming again replaces the
+  // recorder and restarts the count.  std::invalid_argument: check_surface, an
+  // invalid flow index, a ring of more than 2^31 entries.
+  // std::runtime_error: a solver that is one strip of several, or a backend
+  // without a recorder.
+  virtual void record_surface(const SurfaceOpts& o);
+  virtual SurfaceHistory surface_history();
+  virtual const SurfacePlan& surface_plan() const;
+  virtual void clear_surface();
+  // record_surface's checks: the options, and that this solver holds the whole field
+  void check_record_surface(const SurfaceOpts& o) const;
+
  protected:
   // called by advance() after a step the host completed (not the device's asynchronous ones)
   virtual void after_step() {}
@@ -360,6 +378,23 @@ class CpuSolver : public SolverBase {
   std::vector<double> wq_times;     // [capacity]
   std::vector<double> wq_stat;      // m, M, peak, peak_time: [4 nx + ny] each
   std::vector<real> wq_scratch;     // lam + lam_t, Tg, p: [needed cells] each
+
+  // host surface recorder: evaluates the plan on the arrays download() reads
+  void record_surface(const SurfaceOpts& o) override;
+  SurfaceHistory surface_history() override;
+  const SurfacePlan& surface_plan() const override;
+  void clear_surface() override;
+  bool sf_armed = false;
+  SurfaceOpts sf_opts;
+  SurfacePlan sf_plan;
+  StatsScalars sf_sc;
+  long sf_total = 0;
+  void record_surface_step();       // after_step, while armed
+  void sf_rebuild();                // upload(): the plan over the new records (another node count restarts the recorder)
+  std::vector<real> sf_vals;        // [capacity][10][nnodes]
+  std::vector<double> sf_times;     // [capacity]
+  std::vector<double> sf_stat;      // m, M, peak, peak_time: [10][nnodes] each
+  std::vector<real> sf_scratch;     // [SURFACE_PLANES][needed cells]
 
   HostArrays h;
   int gi0, gi1;     // owned global columns

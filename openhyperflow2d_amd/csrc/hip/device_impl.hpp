@@ -136,6 +136,15 @@ struct DeviceSolver::Impl {
   double *wallq_times = nullptr, *wallq_stat = nullptr;
   long wallq_cells_cap = 0, wallq_nodes_cap = 0, wallq_list_cap = 0;
   size_t wallq_vals_cap = 0, wallq_times_cap = 0;
+  SurfaceDev surf{};           // per-step surface recorder (record_surface)
+  // ... its device arrays and their sizes (arming again or a plan rebuilt by upload reuses what fits)
+  long* surf_cells = nullptr;
+  uint8_t *surf_mask = nullptr, *surf_bits = nullptr;
+  int* surf_idx = nullptr;
+  real *surf_scratch = nullptr, *surf_vals = nullptr;
+  double *surf_times = nullptr, *surf_stat = nullptr;
+  long surf_cells_cap = 0, surf_nodes_cap = 0;
+  size_t surf_vals_cap = 0, surf_times_cap = 0, surf_stat_cap = 0;
   FlowStats stats{};           // whole-field statistics (start_averaging)
   size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
   size_t stats_used = 0;       // of which the armed options use (stats_plane_count)

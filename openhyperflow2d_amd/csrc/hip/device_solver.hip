@@ -438,6 +438,7 @@ void DeviceSolver::upload() {
     cp(&m.stats.sc->t_seen, st_clock, sizeof st_clock);
   }
   if (wallq_armed) cp(&m.wallq.sc->s.t_seen, st_clock, sizeof st_clock);   // (the wall heat recorder's weights likewise)
+  if (surf_armed) cp(&m.surf.sc->s.t_seen, st_clock, sizeof st_clock);     // (and the surface recorder's)
   HIP_CHECK(hipStreamSynchronize(st));
   nstep = 0;
   abuf = 0;
@@ -447,6 +448,13 @@ void DeviceSolver::upload() {
   // (the records were replaced: the armed load recorder's cells follow their flags)
   if (loads_cap) loads_plan_rebuild();
   if (wallq_armed) wallq_plan_upload(wallq_plan_build(wallq_opts));   // (and the wall heat recorder's nodes)
+  if (surf_armed) {   // (and the surface recorder's; another node count restarts its ring and statistics)
+    SurfacePlan P = surf_plan_build(surf_opts);
+    const bool same = P.nnodes() == surf_plan.nnodes();
+    if (!same) surf_ring_alloc(P, m.surf.cap);
+    surf_plan_upload(std::move(P));
+    if (!same) surf_reset();
+  }
 }
 
 void DeviceSolver::set_lean_plain(bool on) {
@@ -556,6 +564,25 @@ void DeviceSolver::on_cycle_roll() {
     HIP_CHECK(hipMemcpyAsync(m.wallq.stat + 3 * ne, tp.data() + m.wallq.cap, ne * sizeof(double), hipMemcpyHostToDevice,
                              m.stream));
     HIP_CHECK(hipMemcpyAsync(&m.wallq.sc->s.t_off, &ws.s.t_off, sizeof(double), hipMemcpyHostToDevice, m.stream));
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+  }
+  if (surf_armed) {
+    // likewise the surface recorder's ring times, peak times and clock offset
+    const size_t ne = (size_t)SURFACE_NVARS * surf_plan.nnodes();
+    std::vector<double> tp((size_t)m.surf.cap + ne);
+    WallHeatScalars ws;
+    auto mv = [&](void* d, const void* s, size_t bytes, hipMemcpyKind k) {
+      if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, k, m.stream));
+    };
+    mv(tp.data(), m.surf.times, (size_t)m.surf.cap * sizeof(double), hipMemcpyDeviceToHost);
+    mv(tp.data() + m.surf.cap, m.surf.stat + 3 * ne, ne * sizeof(double), hipMemcpyDeviceToHost);
+    mv(&ws, m.surf.sc, sizeof ws, hipMemcpyDeviceToHost);
+    HIP_CHECK(hipStreamSynchronize(m.stream));
+    for (double& t : tp) t -= T;
+    ws.s.t_off -= T;
+    mv(m.surf.times, tp.data(), (size_t)m.surf.cap * sizeof(double), hipMemcpyHostToDevice);
+    mv(m.surf.stat + 3 * ne, tp.data() + m.surf.cap, ne * sizeof(double), hipMemcpyHostToDevice);
+    mv(&m.surf.sc->s.t_off, &ws.s.t_off, sizeof(double), hipMemcpyHostToDevice);
     HIP_CHECK(hipStreamSynchronize(m.stream));
   }
   if (stats_armed) {
@@ -684,7 +711,9 @@ uint64_t DeviceSolver::mode_signature() const {
                        // (and the load recorder's: record_loads, a plan rebuilt by upload)
                        loads_gen,
                        // (and the wall heat recorder's: record_wall_heat, a plan rebuilt by upload)
-                       wallq_gen};
+                       wallq_gen,
+                       // (and the surface recorder's: record_surface, a plan rebuilt by upload)
+                       surf_gen};
   for (int f : state) mix(f);
   return h;
 }
@@ -870,6 +899,7 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   if (stats_on) launch_stats(P);
   if (loads_cap) launch_loads(P, c.slot, c.slot_next);
   if (wallq_armed) launch_wall_heat(P, c.slot, c.slot_next);
+  if (surf_armed) launch_surface(P, c.slot, c.slot_next);
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;
   StepResult r;
@@ -921,6 +951,8 @@ std::string DeviceSolver::autotune(int steps) {
   loads_cap = 0;
   const bool s_wallq = wallq_armed;   // (nor the wall heat recorder)
   wallq_armed = false;
+  const bool s_surf = surf_armed;     // (nor the surface recorder)
+  surf_armed = false;
   struct Cand {
     int cpt, tj, nt, wgcu = 0;
   };
@@ -1053,6 +1085,7 @@ std::string DeviceSolver::autotune(int steps) {
   stats_on = s_stats;
   loads_cap = s_loads;
   wallq_armed = s_wallq;
+  surf_armed = s_surf;
   upload();   // device scalars from the restored host state
   graph_launches = 0;
   lns_steps = lnm_steps = 0;   // (the tuning steps do not count as the run's)

@@ -130,6 +130,13 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void record_wall_heat(const WallHeatOpts& o) override;
   WallHeatHistory wall_heat_history() override;
   void clear_wall_heat() override;
+  // per-step surface recorder (hip/surface_history.hpp): hf2d_wallq_tick,
+  // hf2d_surf_cells and hf2d_surf_nodes follow the step while armed; reading
+  // the history neither leaves the lean state nor changes a ping-pong parity
+  void record_surface(const SurfaceOpts& o) override;
+  SurfaceHistory surface_history() override;
+  const SurfacePlan& surface_plan() const override;
+  void clear_surface() override;
   void trace_push(const char* name) override;
   void trace_pop() override;
   void synchronize();
@@ -272,6 +279,13 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   bool wallq_armed = false;
   WallHeatOpts wallq_opts;      // what the plan is rebuilt from
   WallHeatPlan wallq_plan;      // host copy of the armed plan
+  int surf_gen = 0;             // arming generation (mode_signature, as probe_gen)
+  bool surf_armed = false;
+  bool surf_friction = false;   // the armed plan holds friction terms (as loads_friction)
+  SurfaceOpts surf_opts;        // what the plan is rebuilt from
+  SurfacePlan surf_plan;        // host copy of the armed plan
+  // the split fills store their gradients every step while a recorder reads them
+  bool friction_recorded() const { return (loads_cap > 0 && loads_friction) || (surf_armed && surf_friction); }
   bool fx_pending = false;   // fused tile steps left the newest ghost columns and dt in the mailbox (p2p_complete)
   // fused lean N-S steps: the last step's halo is still in the mailbox; the
   // next fused step's edge tiles unpack it (lns_ghost_prologue)
@@ -300,6 +314,11 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   WallHeatPlan wallq_plan_build(const WallHeatOpts& o) const;
   void wallq_plan_upload(WallHeatPlan&& P);        // a built plan -> device
   void wallq_reset();                              // ring and statistics empty, the clock at now
+  void launch_surface(const StepParams& P, int slot, int slot_next);   // the surface recorder's three launches
+  SurfacePlan surf_plan_build(const SurfaceOpts& o) const;
+  void surf_plan_upload(SurfacePlan&& P);          // a built plan -> device
+  void surf_ring_alloc(const SurfacePlan& P, int cap);   // ring and statistics arrays for the plan's node count
+  void surf_reset();                               // ring and statistics empty, the clock at now
   void lns_fill_views(SoA& sin, SoA& out) const;   // the views lns_materialize's fill would run over now
   int post_step_view(SoA& s) const;                // PR_* kind and view both of them read
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)

@@ -63,14 +63,17 @@ HF_HD inline void loads_own_cell(const StepParams& P, const SoA& s, const SoA& o
   *rhou = c.S[I_RHOU];
 }
 
-// p, mu, mu_t, dUdy, dVdx of one node as lns_materialize's fill stores them:
-// `fin` is that fill's input view (sin == pold), `out` its output view, whose
-// arrays keep what the fill does not store (fill_cell with store_grad).
-struct LoadsWall {
-  real p, mu, mu_t, dUdy, dVdx;
+// What lns_materialize's fill stores for one cell (lean N-S / mechanism
+// kinds): `fin` is that fill's input view (sin == pold), `out` its output view,
+// whose arrays keep what the fill does not store (fill_cell with store_grad;
+// a solid or unset cell is carried early and keeps everything; SGL stores no
+// lam_t and no mu_t).  One fill_compute per cell: the load recorder, the wall
+// heat recorder and the surface recorder all read their values from this.
+struct WallFill {
+  real p, Tg, lam, lam_t, mu, mu_t, dUdy, dVdx;
 };
 template <int KIND>
-HF_HD inline LoadsWall loads_wall_fill(const StepParams& P, const SoA& fin, const SoA& out, long idx) {
+HF_HD inline WallFill wall_fill_cell(const StepParams& P, const SoA& fin, const SoA& out, long idx) {
   constexpr int MODE = KIND == PR_MECH ? SK_MECH : KIND == PR_SGT ? SK_SGT : SK_SGL;
   constexpr int NSB = KIND == PR_MECH ? 9 : 1;
   const long N = fin.N;
@@ -82,13 +85,32 @@ HF_HD inline LoadsWall loads_wall_fill(const StepParams& P, const SoA& fin, cons
   int neg = 0;
   (void)fill_compute<MODE, NSB>(P, io, c, mY, mgx, mgy, fin.mech, fin.nsp, i, j, io.inplace(out), &neg, &early,
                                 &filled);
-  LoadsWall w;
+  WallFill w;
   const bool grads = !early && !has_all(c.CT, NT_FC) && P.sm == SM_NS;
   w.p = early ? out.p[idx] : c.p;
+  w.Tg = early ? out.Tg[idx] : c.Tg;
+  w.lam = early ? out.lam[idx] : c.lam;
+  w.lam_t = (early || MODE == SK_SGL) ? out.lam_t[idx] : c.lam_t;
   w.mu = early ? out.mu[idx] : c.mu;
   w.mu_t = (early || MODE == SK_SGL) ? out.mu_t[idx] : c.mu_t;
   w.dUdy = grads ? c.dUdy : out.grad[(long)G_DUDY * N + idx];
   w.dVdx = grads ? c.dVdx : out.grad[(long)G_DVDX * N + idx];
+  return w;
+}
+
+// p, mu, mu_t, dUdy, dVdx of one node as lns_materialize's fill stores them
+struct LoadsWall {
+  real p, mu, mu_t, dUdy, dVdx;
+};
+template <int KIND>
+HF_HD inline LoadsWall loads_wall_fill(const StepParams& P, const SoA& fin, const SoA& out, long idx) {
+  const WallFill f = wall_fill_cell<KIND>(P, fin, out, idx);
+  LoadsWall w;
+  w.p = f.p;
+  w.mu = f.mu;
+  w.mu_t = f.mu_t;
+  w.dUdy = f.dUdy;
+  w.dVdx = f.dVdx;
   return w;
 }
 

@@ -1,12 +1,13 @@
 // Observers of the run: monitor points, the per-step probe recorder
 // (probe_history.hpp), the per-step load recorder (load_history.hpp), the
-// per-step wall heat recorder (wall_heat.hpp) and the time-averaged flow
-// statistics (flow_stats.hpp).
+// per-step wall heat recorder (wall_heat.hpp), the per-step surface recorder
+// (surface_history.hpp) and the time-averaged flow statistics (flow_stats.hpp).
 
 #include "device_impl.hpp"
 #include "flow_stats.hpp"
 #include "load_history.hpp"
 #include "wall_heat.hpp"
+#include "surface_history.hpp"
 
 namespace hf2d {
 
@@ -570,6 +571,199 @@ void DeviceSolver::launch_wall_heat(const StepParams& P, int slot, int slot_next
     HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(hf2d_wallq_fold, dim3((unsigned)(L.nx + L.ny)), dim3(WALLQ_BLOCK), 0, m.stream, L, m.sc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Per-step surface recorder (hip/surface_history.hpp)
+// ---------------------------------------------------------------------------
+void DeviceSolver::record_surface(const SurfaceOpts& o) {
+  check_record_surface(o);   // (the options; one strip of several refuses)
+  Impl& m = *impl;
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  // (a refused plan throws here and leaves the armed recorder, if any, whole:
+  // its options, plan, ring and statistics are replaced only together, below)
+  SurfacePlan P = surf_plan_build(o);
+  const int cap = (int)std::min<long>(o.capacity, 0x7fffffffL);
+  surf_ring_alloc(P, cap);
+  SurfaceDev& L = m.surf;
+  if (!L.sc) L.sc = m.mem.alloc<WallHeatScalars>(1);
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  surf_armed = false;
+  surf_plan_upload(std::move(P));
+  surf_opts = o;
+  surf_opts.capacity = cap;
+  L.cap = cap;
+  L.statistics = o.statistics ? 1 : 0;
+  surf_reset();
+  surf_armed = true;
+}
+
+// The plan of the options over the records the backend holds now.  Throws
+// where a value could not be recorded exactly: the wall heat recorder's
+// refusals (wallq_plan_build), for the same reasons.
+SurfacePlan DeviceSolver::surf_plan_build(const SurfaceOpts& o) const {
+  SurfacePlan P = build_surface_plan(cs, cs.J, o, l_off);
+  for (long c : P.cells)
+    if (c < 0 || c >= h.N) throw std::runtime_error("surface recorder: a needed cell lies outside the solver's arrays");
+  if (P.nnodes() > 0 && (lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset &&
+      cs.cfg.TurbStartIter >= 2 && last_iter + iter < (long)cs.cfg.TurbStartIter)
+    throw std::runtime_error("surface recorder: wall nodes on the lean N-S / mechanism state cannot be recorded "
+                             "exactly before TurbStartIter has passed; arm (or upload) later");
+  if (P.nnodes() > 0 && lean_ok && !lean_sg_ok && make_params(last_iter + iter).chem_model != NO_REACTIONS)
+    throw std::runtime_error("surface recorder: a reacting gas mixture on the lean inviscid step stores no wall "
+                             "temperature between outputs; the recorder cannot be armed on this deck");
+  return P;
+}
+
+// Ring and statistics arrays for the plan's node count and `cap` rows (used
+// again where they are large enough).
+void DeviceSolver::surf_ring_alloc(const SurfacePlan& P, int cap) {
+  Impl& m = *impl;
+  const size_t ne = (size_t)SURFACE_NVARS * P.nnodes(), nv = (size_t)cap * ne;
+  if (nv > m.surf_vals_cap) {
+    m.surf_vals = m.mem.alloc<real>(nv);
+    m.surf_vals_cap = nv;
+  }
+  if ((size_t)cap > m.surf_times_cap) {
+    m.surf_times = m.mem.alloc<double>((size_t)cap);
+    m.surf_times_cap = (size_t)cap;
+  }
+  if (4 * ne > m.surf_stat_cap) {
+    m.surf_stat = m.mem.alloc<double>(4 * ne);
+    m.surf_stat_cap = 4 * ne;
+  }
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  m.surf.vals = m.surf_vals;
+  m.surf.times = m.surf_times;
+  m.surf.stat = m.surf_stat;
+}
+
+// A built plan into the device arrays (used again where they are large
+// enough; the stream is idle: flush_pending / upload synchronised it).
+void DeviceSolver::surf_plan_upload(SurfacePlan&& P) {
+  Impl& m = *impl;
+  const long nc = P.ncells(), nn = P.nnodes();
+  if (nc > m.surf_cells_cap) {
+    m.surf_cells = m.mem.alloc<long>((size_t)nc);
+    m.surf_mask = m.mem.alloc<uint8_t>((size_t)nc);
+    m.surf_scratch = m.mem.alloc<real>((size_t)SURFACE_PLANES * nc);
+    m.surf_cells_cap = nc;
+  }
+  if (nn > m.surf_nodes_cap) {
+    m.surf_idx = m.mem.alloc<int>((size_t)SURFACE_IDX * nn);
+    m.surf_bits = m.mem.alloc<uint8_t>((size_t)nn);
+    m.surf_nodes_cap = nn;
+  }
+  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets, and nothing in flight reads the arrays)
+  auto cp = [&](void* d, const void* s, size_t bytes) {
+    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, m.stream));
+  };
+  cp(m.surf_cells, P.cells.data(), nc * sizeof(long));
+  cp(m.surf_mask, P.mask.data(), nc * sizeof(uint8_t));
+  cp(m.surf_idx, P.idx.data(), (size_t)SURFACE_IDX * nn * sizeof(int));
+  cp(m.surf_bits, P.bits.data(), nn * sizeof(uint8_t));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  SurfaceDev& L = m.surf;
+  L.K = P.K;
+  L.cells = m.surf_cells;
+  L.mask = m.surf_mask;
+  L.idx = m.surf_idx;
+  L.bits = m.surf_bits;
+  L.scratch = m.surf_scratch;
+  L.ncells = nc;
+  L.nnodes = nn;
+  surf_plan = std::move(P);
+  surf_friction = surf_plan.friction();
+  surf_gen++;   // windows captured so far must not replay (mode_signature)
+}
+
+// An empty ring and empty statistics whose clock starts at the present value.
+void DeviceSolver::surf_reset() {
+  Impl& m = *impl;
+  WallHeatScalars s0{};
+  s0.s.every = surf_opts.every;
+  s0.s.step_weight = surf_opts.step_weight ? 1 : 0;
+  s0.s.t_off = time_offset;
+  HIP_CHECK(hipMemcpyAsync(m.surf.sc, &s0, sizeof s0, hipMemcpyHostToDevice, m.stream));
+  const size_t ne = (size_t)SURFACE_NVARS * surf_plan.nnodes();
+  if (ne) HIP_CHECK(hipMemsetAsync(m.surf.stat, 0, 4 * ne * sizeof(double), m.stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, &m.surf.sc->s, m.sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+}
+
+void DeviceSolver::clear_surface() {
+  if (!surf_armed) return;
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  surf_reset();
+}
+
+const SurfacePlan& DeviceSolver::surface_plan() const {
+  if (!surf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
+  return surf_plan;
+}
+
+SurfaceHistory DeviceSolver::surface_history() {
+  if (!surf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const SurfaceDev& L = m.surf;
+  const size_t ne = (size_t)SURFACE_NVARS * surf_plan.nnodes();
+  WallHeatScalars ws;
+  std::vector<real> vals((size_t)L.cap * ne);
+  std::vector<double> tp((size_t)L.cap), stat(4 * ne);
+  HIP_CHECK(hipMemcpyAsync(&ws, L.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
+  if (!vals.empty())
+    HIP_CHECK(hipMemcpyAsync(vals.data(), L.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+  if (!tp.empty())
+    HIP_CHECK(hipMemcpyAsync(tp.data(), L.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  if (!stat.empty())
+    HIP_CHECK(hipMemcpyAsync(stat.data(), L.stat, stat.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  // (the probe ring's clock: probe_history)
+  return surface_history_from(surf_plan, surf_opts, vals.data(), tp.data(), (long)ws.s.samples, stat.data(), ws.s,
+                              [&](double t) {
+                                const real part = t - time_offset;
+                                return (double)(cs.global_time + part);
+                              });
+}
+
+// After the other observers' launches; the same view, and for the lean N-S /
+// mechanism state the materialise fill's (as launch_loads).  Nothing here
+// allocates, copies or synchronises.
+void DeviceSolver::launch_surface(const StepParams& P, int slot, int slot_next) {
+  Impl& m = *impl;
+  SoA s;
+  const int kind = post_step_view(s);
+  SoA fin = s, out = s;
+  // the dt slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3, else (nstep + 2) % 3)
+  int fslot = slot;
+  if (lns_state) {
+    lns_fill_views(fin, out);
+    if (kind == PR_SGL) fslot = slot_next;
+  }
+  const SurfaceDev& L = m.surf;
+  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.sc, m.sc, L.cap);
+  HIP_CHECK(hipGetLastError());
+  if (L.ncells > 0) {
+    const dim3 g((unsigned)((L.ncells + SURF_BLOCK - 1) / SURF_BLOCK)), b(SURF_BLOCK);
+    switch (kind) {
+      case PR_SGL: hipLaunchKernelGGL(hf2d_surf_cells<PR_SGL>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_SGT: hipLaunchKernelGGL(hf2d_surf_cells<PR_SGT>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_MECH: hipLaunchKernelGGL(hf2d_surf_cells<PR_MECH>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      case PR_LEAN: hipLaunchKernelGGL(hf2d_surf_cells<PR_LEAN>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+      default: hipLaunchKernelGGL(hf2d_surf_cells<PR_GATHER>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  // (at least one workgroup: the sample's time is written for a plan without nodes too)
+  const long gn = L.nnodes > 0 ? (L.nnodes + SURF_BLOCK - 1) / SURF_BLOCK : 1;
+  hipLaunchKernelGGL(hf2d_surf_nodes, dim3((unsigned)gn), dim3(SURF_BLOCK), 0, m.stream, L, m.sc);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -6,6 +6,7 @@
 
 #include "../core/lean_euler.hpp"
 #include "../core/wall_heat.hpp"
+#include "../core/surface_plan.hpp"
 
 namespace hf2d {
 
@@ -131,6 +132,24 @@ struct WallHeatDev {
   real* vals = nullptr;          // [cap][4 nx + ny]
   double* times = nullptr;       // [cap] DevScalars::time_part after the step
   double* stat = nullptr;        // [4][4 nx + ny] m, M, peak, peak_time (DevScalars::time_part)
+  WallHeatScalars* sc = nullptr;
+};
+
+// Per-step surface recorder (surface_history.hpp): the plan, the ring and the
+// statistics; the tick's scalars are the wall heat recorder's kind, its own
+struct SurfaceDev {
+  WallHeatConst K;
+  // the plan (SurfacePlan)
+  const long* cells = nullptr;     // [ncells]
+  const uint8_t* mask = nullptr;   // [ncells] SurfaceCellBit
+  const int* idx = nullptr;        // [nnodes][SURFACE_IDX]
+  const uint8_t* bits = nullptr;   // [nnodes] SurfaceNodeBit
+  long ncells = 0, nnodes = 0;
+  int cap = 0, statistics = 0;
+  real* scratch = nullptr;         // [SURFACE_PLANES][ncells] the needed cells' values after the step
+  real* vals = nullptr;            // [cap][SURFACE_NVARS][nnodes]
+  double* times = nullptr;         // [cap] DevScalars::time_part after the step
+  double* stat = nullptr;          // [4][SURFACE_NVARS][nnodes] m, M, peak, peak_time (DevScalars::time_part)
   WallHeatScalars* sc = nullptr;
 };
 

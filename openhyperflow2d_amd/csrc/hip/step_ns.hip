@@ -251,7 +251,7 @@ DeviceSolver::StepDone DeviceSolver::step_split(const StepCtx& c, bool to_lns) {
     }
     // SGL: gradients / Diff only when the host reads the record (or y+ follows)
     // (or the armed load recorder folds wall friction after every step: stores only, same values)
-    const int sg_out = (step_outputs || want_res || (loads_cap > 0 && loads_friction)) ? 1 : 0;
+    const int sg_out = (step_outputs || want_res || friction_recorded()) ? 1 : 0;
     // SGT / mechanism: the gradients an active N-S cell stores are recomputed
     // by its next fill before any use (fill_compute), so between outputs
     // (and the wall friction velocities of the cycle end, an output step) they

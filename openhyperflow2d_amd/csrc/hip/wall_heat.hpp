@@ -66,22 +66,10 @@ HF_HD inline void wallq_cell(const StepParams& P, const SoA& s, const SoA& fin, 
       *Tg = row[1];
     }
   } else {
-    constexpr int MODE = KIND == PR_MECH ? SK_MECH : KIND == PR_SGT ? SK_SGT : SK_SGL;
-    constexpr int NSB = KIND == PR_MECH ? 9 : 1;
-    const int i = (int)(idx / P.ny), j = (int)(idx - (long)i * P.ny);
-    FillSoAIO io(fin, fin, idx);
-    CellLocal c;
-    real mY[NSB], mgx[NSB], mgy[NSB];
-    bool early, filled;
-    int neg = 0;
-    (void)fill_compute<MODE, NSB>(P, io, c, mY, mgx, mgy, fin.mech, fin.nsp, i, j, io.inplace(out), &neg, &early,
-                                  &filled);
-    // (fill_cell's stores; what it does not store keeps the output view's value)
-    const real lam = early ? out.lam[idx] : c.lam;
-    const real lam_t = (early || MODE == SK_SGL) ? out.lam_t[idx] : c.lam_t;
-    *sl = lam + lam_t;
-    *Tg = early ? out.Tg[idx] : c.Tg;
-    *p = early ? out.p[idx] : c.p;
+    const WallFill f = wall_fill_cell<KIND>(P, fin, out, idx);
+    *sl = f.lam + f.lam_t;
+    *Tg = f.Tg;
+    *p = f.p;
   }
 }
 

@@ -46,6 +46,8 @@ def parse_fault(spec: str):
 
 PROBE_VARS = ("p", "T", "rho", "U", "V")   # column order of Simulation.probe_history()["values"]
 LOAD_PARTS = ("Fx_p", "Fx_d", "Fy_p", "Fy_d")   # last axis of Simulation.load_history()["forces"]
+# row order of Case.surface()["values"] and of Simulation.surface_history()["values"]
+SURFACE_VARS = ("p", "Cp", "T", "tau_x", "tau_y", "Cf_x", "Cf_y", "q_y", "q_x", "St")
 WALL_HEAT_X = ("Q", "Alpha", "Cp", "St")   # rows of Case.heat_flux_x() and of Simulation.wall_heat_history()["x"]
 
 
@@ -233,6 +235,56 @@ class Simulation:
     def clear_wall_heat(self) -> None:
         """Empty the ring and the statistics; the recorder stays armed."""
         self.solver.clear_wall_heat()
+
+    # -- per-step surface recorder ---------------------------------------------
+    def record_surface(self, boxes=None, cp_flow=None, every: int = 1, capacity: int = 1024,
+                       statistics: bool = True, weight: str = "time") -> None:
+        """Arm the per-step surface recorder: ``SURFACE_VARS = ("p", "Cp",
+        "T", "tau_x", "tau_y", "Cf_x", "Cf_y", "q_y", "q_x", "St")`` of every
+        wall node.
+
+        A node is a set, non-solid cell that is a no-slip or wall-law wall or
+        has a solid 4-neighbour.  ``boxes`` (at most 16, each ``(x0, y0, dx,
+        dy)`` as for ``record_loads``) lists the nodes of each box in turn, in
+        ``(i, j)`` order; ``boxes=None`` lists every node.  From now on every
+        ``every``-th step appends the ten values of every listed node and the
+        step's time to a ring of ``capacity`` rows kept by the backend
+        (``capacity=0``: statistics only), and with ``statistics`` folds every
+        entry into a running mean, variance, peak and peak time (``weight``:
+        ``"time"`` or ``"step"``).  Every value is bit for bit
+        ``case.surface(boxes, cp_flow)["values"]`` on a field downloaded after
+        that step.  ``cp_flow`` (1-based) defaults to the deck's
+        ``Cp_Flow_Index``.  On the GPU three small kernels run at the end of
+        each step, inside the step graphs, and the lean states are never
+        materialised.  Arming again replaces the recorder.  ``ValueError``:
+        more than 16 boxes, a box that is not finite, ``every < 1``,
+        ``capacity < 0``, ``capacity == 0`` without statistics, an unknown
+        ``weight``, a flow index the case does not have, a ring of more than
+        2^31 entries.  ``RuntimeError``: the solver is one strip of several,
+        or the values could not be recorded exactly (see the README)."""
+        if weight not in ("time", "step"):
+            raise ValueError("record_surface: weight is 'time' or 'step', not %r" % (weight,))
+        f = int(self.case.wall_heat_keys["Cp_Flow_Index"] if cp_flow is None else cp_flow)
+        b = None if boxes is None else [tuple(float(v) for v in q) for q in boxes]
+        self.solver.record_surface(b, f, int(every), int(capacity), bool(statistics), weight == "step")
+
+    def surface_history(self) -> dict:
+        """The recorded samples, oldest first: ``times`` [n] (the clock of
+        ``probe_history()``), ``values`` [n, 10, nnodes] in ``SURFACE_VARS``
+        order, ``total`` (samples taken since arming; n = min(total,
+        capacity)), the static node table (``i``, ``j``, ``x``, ``y``,
+        ``flags``, ``face_x``, ``face_y``, ``fric_x``, ``fric_y`` [nnodes],
+        ``box_off`` [nboxes + 1]) and with statistics ``mean``, ``var``,
+        ``peak``, ``peak_time`` [10, nnodes], ``time`` (the weight sum) and
+        ``samples``.  Reading does not disturb the solver state."""
+        h = dict(self.solver.surface_history())
+        for k, v in h.items():
+            h[k] = int(v) if k in ("total", "samples") else float(v) if k == "time" else np.asarray(v)
+        return h
+
+    def clear_surface(self) -> None:
+        """Empty the ring and the statistics; the recorder stays armed."""
+        self.solver.clear_surface()
 
     # -- time-averaged flow statistics ---------------------------------------
     def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time",
