@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "postproc.hpp"
+#include "ring_history.hpp"
 #include "stepkern.hpp"
 
 namespace hf2d {
@@ -216,25 +217,22 @@ inline LoadPlan build_load_plan(const Case& cs, const Field& J, const std::vecto
   return L;
 }
 
-// Ring of list values: row s holds the nlists() folds of one step.
-// -> LoadHistory, oldest first; time_of(slot): the step's time.
+// Ring of list values: row s holds the nlists() folds of one step, times[s]
+// its time.  -> LoadHistory, oldest first; time_of(t): the reader's clock.
 template <class TimeOf>
-inline LoadHistory load_history_from_ring(const LoadPlan& L, const real* vals, long total, long cap, TimeOf time_of) {
+inline LoadHistory load_history_from_ring(const LoadPlan& L, const real* vals, const double* times, long total, long cap,
+                                          TimeOf time_of) {
   LoadHistory H;
   H.nboxes = L.nboxes;
   H.ncuts = L.ncuts;
   H.total = total;
-  const long n = std::min(total, cap), first = total > cap ? total % cap : 0;
   const size_t nl = (size_t)L.nlists(), nf = (size_t)LOAD_PARTS * L.nboxes;
-  H.times.resize(n);
-  H.forces.resize((size_t)n * nf);
-  H.mass_flow.resize((size_t)n * L.ncuts);
-  for (long k = 0; k < n; k++) {
-    const long s = (first + k) % cap;
-    H.times[k] = time_of(s);
-    const real* row = vals + (size_t)s * nl;
-    std::copy(row, row + nf, H.forces.begin() + (size_t)k * nf);
-    std::copy(row + nf, row + nl, H.mass_flow.begin() + (size_t)k * L.ncuts);
+  std::vector<real> rows;
+  ring_oldest_first(vals, nl, times, total, cap, time_of, rows, H.times);
+  for (size_t k = 0; k < H.times.size(); k++) {
+    const real* row = rows.data() + k * nl;
+    H.forces.insert(H.forces.end(), row, row + nf);
+    H.mass_flow.insert(H.mass_flow.end(), row + nf, row + nl);
   }
   for (size_t l = 0; l < nl; l++) (l < nf ? H.box_terms : H.cut_terms).push_back(L.off[l + 1] - L.off[l]);
   H.span = L.span;

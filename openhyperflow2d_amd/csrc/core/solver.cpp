@@ -908,8 +908,8 @@ void CpuSolver::clear_load_history() { load_total = 0; }
 
 LoadHistory CpuSolver::load_history() {
   if (load_cap == 0) throw std::runtime_error("load_history: no recorder armed (record_loads)");
-  return load_history_from_ring(load_plan, load_vals.data(), load_total, load_cap,
-                                [&](long s) { return load_times[s]; });
+  return load_history_from_ring(load_plan, load_vals.data(), load_times.data(), load_total, load_cap,
+                                [](double t) { return t; });
 }
 
 // the values download() would put into the records now: the lean inviscid
@@ -1053,28 +1053,22 @@ void CpuSolver::record_wall_heat(const WallHeatOpts& o) {
   WallHeatPlan P = build_wall_heat_plan(cs, cs.J, o, l_off);
   wq_plan = std::move(P);
   wq_opts = o;
-  wq_vals.assign((size_t)o.capacity * wq_plan.nentries(), 0.0);
-  wq_times.assign((size_t)o.capacity, 0.0);
+  wq.vals.assign((size_t)o.capacity * wq_plan.nentries(), 0.0);
+  wq.times.assign((size_t)o.capacity, 0.0);
   wq_scratch.assign(3 * (size_t)wq_plan.ncells(), 0.0);
   wq_armed = true;
   clear_wall_heat();
 }
 
-// the ring and the statistics restart; the sampling count and the clock with them
 void CpuSolver::clear_wall_heat() {
-  if (!wq_armed) return;
-  wq_total = 0;
-  wq_sc = StatsScalars{};
-  wq_sc.every = wq_opts.every;
-  wq_sc.step_weight = wq_opts.step_weight ? 1 : 0;
-  wq_sc.t_seen = (double)(cs.global_time + cur_time_part);
-  wq_stat.assign(4 * (size_t)wq_plan.nentries(), 0.0);
+  if (wq_armed)
+    wq.clear((size_t)wq_plan.nentries(), wq_opts.every, wq_opts.step_weight, (double)(cs.global_time + cur_time_part));
 }
 
 // the needed cells from the arrays download() would copy, then every list folded in list order
 void CpuSolver::record_wall_heat_step() {
   const double t = (double)(cs.global_time + cur_time_part);
-  if (!stats_tick(wq_sc, t)) return;
+  if (!stats_tick(wq.sc, t)) return;
   const WallHeatPlan& L = wq_plan;
   const size_t nc = (size_t)L.ncells(), ne = (size_t)L.nentries();
   const real* p = lean_state ? P2[pbuf].data() : h.p.data();
@@ -1086,26 +1080,25 @@ void CpuSolver::record_wall_heat_step() {
     sp[k] = p[c];
   }
   const long cap = wq_opts.capacity;
-  const long slot = cap ? wq_total % cap : 0;
-  double *m = wq_stat.data(), *M = m + ne, *pk = M + ne, *pt = pk + ne;
+  const long slot = cap ? wq.total % cap : 0;
+  double *m = wq.stat.data(), *M = m + ne, *pk = M + ne, *pt = pk + ne;
   for (int l = 0; l < L.nlists(); l++) {
     real out[WALL_HEAT_X];
     wall_heat_list(L.K, L.nx, l, L.off.data(), L.list.data(), L.node5.data(), sl, sT, sp, out);
     for (int k = 0; k < (l < L.nx ? WALL_HEAT_X : 1); k++) {
       const int e = wall_heat_entry(L.nx, l, k);
-      if (cap) wq_vals[(size_t)slot * ne + e] = out[k];
+      if (cap) wq.vals[(size_t)slot * ne + e] = out[k];
       if (wq_opts.statistics)
-        wall_heat_stat(wq_sc.w, wq_sc.r, t, wq_sc.samples == 1, (double)out[k], m[e], M[e], pk[e], pt[e]);
+        wall_heat_stat(wq.sc.w, wq.sc.r, t, wq.sc.samples == 1, (double)out[k], m[e], M[e], pk[e], pt[e]);
     }
   }
-  if (cap) wq_times[slot] = t;
-  wq_total++;
+  if (cap) wq.times[slot] = t;
+  wq.total++;
 }
 
 WallHeatHistory CpuSolver::wall_heat_history() {
   if (!wq_armed) throw std::runtime_error("wall_heat_history: no recorder armed (record_wall_heat)");
-  return wall_heat_history_from(wq_plan, wq_opts, wq_vals.data(), wq_times.data(), wq_total, wq_stat.data(), wq_sc,
-                                [](double t) { return t; });
+  return wall_heat_history_from(wq_plan, wq_opts, wq, [](double t) { return t; });
 }
 
 void CpuSolver::record_surface(const SurfaceOpts& o) {
@@ -1114,30 +1107,23 @@ void CpuSolver::record_surface(const SurfaceOpts& o) {
   SurfacePlan P = build_surface_plan(cs, cs.J, o, l_off);
   sf_plan = std::move(P);
   sf_opts = o;
-  sf_vals.assign((size_t)o.capacity * SURFACE_NVARS * sf_plan.nnodes(), 0.0);
-  sf_times.assign((size_t)o.capacity, 0.0);
+  sf.vals.assign((size_t)o.capacity * sf_plan.nentries(), 0.0);
+  sf.times.assign((size_t)o.capacity, 0.0);
   sf_scratch.assign((size_t)SURFACE_PLANES * sf_plan.ncells(), 0.0);
   sf_armed = true;
   clear_surface();
 }
 
-// the ring and the statistics restart; the sampling count and the clock with them
 void CpuSolver::clear_surface() {
-  if (!sf_armed) return;
-  sf_total = 0;
-  sf_sc = StatsScalars{};
-  sf_sc.every = sf_opts.every;
-  sf_sc.step_weight = sf_opts.step_weight ? 1 : 0;
-  sf_sc.t_seen = (double)(cs.global_time + cur_time_part);
-  sf_stat.assign(4 * (size_t)SURFACE_NVARS * sf_plan.nnodes(), 0.0);
+  if (sf_armed) sf.clear(sf_plan.nentries(), sf_opts.every, sf_opts.step_weight, (double)(cs.global_time + cur_time_part));
 }
 
 // the needed cells from the arrays download() would copy, then every node's ten values
 void CpuSolver::record_surface_step() {
   const double t = (double)(cs.global_time + cur_time_part);
-  if (!stats_tick(sf_sc, t)) return;
+  if (!stats_tick(sf.sc, t)) return;
   const SurfacePlan& L = sf_plan;
-  const size_t nc = (size_t)L.ncells(), ne = (size_t)SURFACE_NVARS * L.nnodes();
+  const size_t nc = (size_t)L.ncells(), ne = L.nentries();
   const real* p = lean_state ? P2[pbuf].data() : h.p.data();
   const real* gU = h.grad.data() + (size_t)G_DUDY * h.N;
   const real* gV = h.grad.data() + (size_t)G_DVDX * h.N;
@@ -1155,11 +1141,11 @@ void CpuSolver::record_surface_step() {
     sc[SP_V * nc + k] = h.V[pbuf][c];
   }
   const long cap = sf_opts.capacity;
-  const long slot = cap ? sf_total % cap : 0;
-  surface_sample(L, sc, cap ? sf_vals.data() + (size_t)slot * ne : nullptr,
-                 sf_opts.statistics ? sf_stat.data() : nullptr, sf_sc, t);
-  if (cap) sf_times[slot] = t;
-  sf_total++;
+  const long slot = cap ? sf.total % cap : 0;
+  surface_sample(L, sc, cap ? sf.vals.data() + (size_t)slot * ne : nullptr,
+                 sf_opts.statistics ? sf.stat.data() : nullptr, sf.sc, t);
+  if (cap) sf.times[slot] = t;
+  sf.total++;
 }
 
 // upload() replaced the records: the same options over the new flags.  The
@@ -1170,14 +1156,13 @@ void CpuSolver::sf_rebuild() {
   sf_plan = build_surface_plan(cs, cs.J, sf_opts, l_off);
   sf_scratch.assign((size_t)SURFACE_PLANES * sf_plan.ncells(), 0.0);
   if (sf_plan.nnodes() == nn) return;
-  sf_vals.assign((size_t)sf_opts.capacity * SURFACE_NVARS * sf_plan.nnodes(), 0.0);
+  sf.vals.assign((size_t)sf_opts.capacity * sf_plan.nentries(), 0.0);
   clear_surface();
 }
 
 SurfaceHistory CpuSolver::surface_history() {
   if (!sf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
-  return surface_history_from(sf_plan, sf_opts, sf_vals.data(), sf_times.data(), sf_total, sf_stat.data(), sf_sc,
-                              [](double t) { return t; });
+  return surface_history_from(sf_plan, sf_opts, sf, [](double t) { return t; });
 }
 const SurfacePlan& CpuSolver::surface_plan() const {
   if (!sf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
@@ -1190,14 +1175,8 @@ ProbeHistory CpuSolver::probe_history() {
   const size_t np = probe_idx.size(), row = np * PROBE_HISTORY_VARS;
   H.nprobes = (int)np;
   H.total = probe_total;
-  const long n = std::min(probe_total, probe_cap), first = probe_total > probe_cap ? probe_total % probe_cap : 0;
-  H.times.resize(n);
-  H.values.resize((size_t)n * row);
-  for (long k = 0; k < n; k++) {
-    const long s = (first + k) % probe_cap;
-    H.times[k] = probe_times[s];
-    std::copy(probe_rows.begin() + s * row, probe_rows.begin() + (s + 1) * row, H.values.begin() + k * row);
-  }
+  ring_oldest_first(probe_rows.data(), row, probe_times.data(), probe_total, probe_cap, [](double t) { return t; },
+                    H.values, H.times);
   H.owned.resize(np);
   for (size_t q = 0; q < np; q++) H.owned[q] = probe_idx[q] >= 0 ? 1 : 0;
   return H;

@@ -371,12 +371,8 @@ class CpuSolver : public SolverBase {
   bool wq_armed = false;
   WallHeatOpts wq_opts;
   WallHeatPlan wq_plan;
-  StatsScalars wq_sc;
-  long wq_total = 0;
+  SampledRing wq;                   // entries: the profiles' 4 nx + ny
   void record_wall_heat_step();     // after_step, while armed
-  std::vector<real> wq_vals;        // [capacity][4 nx + ny]
-  std::vector<double> wq_times;     // [capacity]
-  std::vector<double> wq_stat;      // m, M, peak, peak_time: [4 nx + ny] each
   std::vector<real> wq_scratch;     // lam + lam_t, Tg, p: [needed cells] each
 
   // host surface recorder: evaluates the plan on the arrays download() reads
@@ -387,13 +383,9 @@ class CpuSolver : public SolverBase {
   bool sf_armed = false;
   SurfaceOpts sf_opts;
   SurfacePlan sf_plan;
-  StatsScalars sf_sc;
-  long sf_total = 0;
+  SampledRing sf;                   // entries: [10][nnodes]
   void record_surface_step();       // after_step, while armed
   void sf_rebuild();                // upload(): the plan over the new records (another node count restarts the recorder)
-  std::vector<real> sf_vals;        // [capacity][10][nnodes]
-  std::vector<double> sf_times;     // [capacity]
-  std::vector<double> sf_stat;      // m, M, peak, peak_time: [10][nnodes] each
   std::vector<real> sf_scratch;     // [SURFACE_PLANES][needed cells]
 
   HostArrays h;

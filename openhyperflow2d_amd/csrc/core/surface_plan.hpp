@@ -83,6 +83,7 @@ struct SurfacePlan {
   std::vector<real> x, y, face_x, face_y, fric_x, fric_y;
   std::vector<long> box_off;     // [nboxes + 1]
   long nnodes() const { return (long)bits.size(); }
+  size_t nentries() const { return (size_t)SURFACE_NVARS * bits.size(); }
   long ncells() const { return (long)cells.size(); }
   bool friction() const {
     for (uint8_t b : bits)
@@ -91,17 +92,10 @@ struct SurfacePlan {
   }
 };
 
-// What surface_history() returns: row k holds the values after sampled step k,
-// oldest first.
-struct SurfaceHistory {
+// What surface_history() returns: an entry is one variable of one node, a row
+// [SURFACE_NVARS][nnodes].
+struct SurfaceHistory : SampledHistory {
   long nnodes = 0;
-  long total = 0;                // samples taken since arming (rows kept: min(total, capacity))
-  std::vector<double> times;     // [n]
-  std::vector<real> vals;        // [n][SURFACE_NVARS][nnodes]
-  bool statistics = false;
-  std::vector<double> mean, var, peak, peak_time;   // [SURFACE_NVARS][nnodes]
-  double time = 0.0;
-  long samples = 0;
 };
 
 // The ten values of one node from what a download after the step holds.
@@ -295,38 +289,13 @@ inline void surface_sample(const SurfacePlan& P, const real* sc, real* row, doub
   }
 }
 
-// Ring and statistics -> SurfaceHistory, oldest first; time_of(t): the
-// reader's clock for a stored time.  stat: m, M, peak, peak_time [ne] each.
+// Ring and statistics -> SurfaceHistory, oldest first (sampled_history_fill).
 template <class TimeOf>
-inline SurfaceHistory surface_history_from(const SurfacePlan& P, const SurfaceOpts& o, const real* vals,
-                                           const double* times, long total, const double* stat,
-                                           const StatsScalars& sc, TimeOf time_of) {
+inline SurfaceHistory surface_history_from(const SurfacePlan& P, const SurfaceOpts& o, const SampledRing& r,
+                                           TimeOf time_of) {
   SurfaceHistory H;
   H.nnodes = P.nnodes();
-  H.total = total;
-  const long cap = o.capacity;
-  const size_t ne = (size_t)SURFACE_NVARS * P.nnodes();
-  const long n = cap ? std::min(total, cap) : 0, first = cap && total > cap ? total % cap : 0;
-  H.times.resize(n);
-  H.vals.resize((size_t)n * ne);
-  for (long k = 0; k < n; k++) {
-    const long s = (first + k) % cap;
-    H.times[k] = time_of(times[s]);
-    if (ne) std::copy(vals + (size_t)s * ne, vals + (size_t)(s + 1) * ne, H.vals.begin() + (size_t)k * ne);
-  }
-  H.statistics = o.statistics;
-  if (o.statistics) {
-    H.time = sc.W;
-    H.samples = (long)sc.samples;
-    H.mean.assign(stat, stat + ne);
-    H.var.assign(stat + ne, stat + 2 * ne);
-    H.peak.assign(stat + 2 * ne, stat + 3 * ne);
-    H.peak_time.assign(ne, 0.0);
-    for (size_t k = 0; k < ne; k++) {
-      H.var[k] = sc.samples ? H.var[k] / sc.W : 0.0;
-      if (sc.samples) H.peak_time[k] = time_of(stat[3 * ne + k]);
-    }
-  }
+  sampled_history_fill(H, r, o.capacity, P.nentries(), o.statistics, time_of);
   return H;
 }
 

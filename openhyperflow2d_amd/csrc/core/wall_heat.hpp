@@ -37,6 +37,7 @@
 
 #include "case.hpp"
 #include "flow_stats.hpp"
+#include "ring_history.hpp"
 
 namespace hf2d {
 
@@ -130,18 +131,65 @@ inline std::pair<int, int> wall_heat_rows(int y_min, int y_max, int ny) {
   return {std::max(0, y_min), std::min(y_max, ny - 1)};
 }
 
-// What wall_heat_history() returns: row k holds the profiles after sampled
-// step k, oldest first.
-struct WallHeatHistory {
-  int nx = 0, ny = 0;
+// A ring of sampled rows of `ne` entries with the running statistics of every
+// entry, on the host: the CPU backend's recorders keep theirs in one, and a
+// device recorder's is read back into one.  The wall heat recorder and the
+// surface recorder (surface_plan.hpp) differ only in what an entry is.
+struct SampledRing {
+  std::vector<real> vals;      // [capacity][ne]
+  std::vector<double> times;   // [capacity] time after the sampled step
+  std::vector<double> stat;    // m, M, peak, peak_time: [ne] each
+  StatsScalars sc;             // the sampling decision and the weights (stats_tick)
+  long total = 0;              // samples taken since arming
+  // the ring and the statistics restart; the sampling count and the clock (at t_now) with them
+  void clear(size_t ne, int every, bool step_weight, double t_now) {
+    total = 0;
+    sc = StatsScalars{};
+    sc.every = every;
+    sc.step_weight = step_weight ? 1 : 0;
+    sc.t_seen = t_now;
+    stat.assign(4 * ne, 0.0);
+  }
+};
+
+// What both recorders' histories hold: row k of vals is sample k, oldest first.
+struct SampledHistory {
   long total = 0;              // samples taken since arming (rows kept: min(total, capacity))
   std::vector<double> times;   // [n] time after the step (the probe recorder's clock)
-  std::vector<real> vals;      // [n][4 nx + ny]: Q, Alpha, Cp, St [nx] each, then the Y profile [ny]
-  std::vector<long> x_nodes, y_nodes;   // [nx], [ny] nodes of each list (static)
+  std::vector<real> vals;      // [n][ne]
   bool statistics = false;
-  std::vector<double> mean, var, peak, peak_time;   // [4 nx + ny] each
+  std::vector<double> mean, var, peak, peak_time;   // [ne] each
   double time = 0.0;           // W: the weighted time span, or the sample count
   long samples = 0;
+};
+
+// Ring and statistics -> history; time_of(t): the reader's clock for a stored time.
+template <class TimeOf>
+inline void sampled_history_fill(SampledHistory& H, const SampledRing& r, long cap, size_t ne, bool statistics,
+                                 TimeOf time_of) {
+  H.total = r.total;
+  ring_oldest_first(r.vals.data(), ne, r.times.data(), r.total, cap, time_of, H.vals, H.times);
+  H.statistics = statistics;
+  if (!statistics) return;
+  const StatsScalars& sc = r.sc;
+  const double* stat = r.stat.data();
+  H.time = sc.W;
+  H.samples = (long)sc.samples;
+  H.mean.assign(stat, stat + ne);
+  H.var.assign(stat + ne, stat + 2 * ne);
+  H.peak.assign(stat + 2 * ne, stat + 3 * ne);
+  H.peak_time.assign(ne, 0.0);
+  for (size_t k = 0; k < ne; k++) {
+    H.var[k] = sc.samples ? H.var[k] / sc.W : 0.0;
+    if (sc.samples) H.peak_time[k] = time_of(stat[3 * ne + k]);
+  }
+}
+
+// What wall_heat_history() returns: an entry is a profile value, a row
+// Q, Alpha, Cp, St [nx] each, then the Y profile [ny].
+struct WallHeatHistory : SampledHistory {
+  int nx = 0, ny = 0;
+  std::vector<long> x_nodes, y_nodes;   // [nx], [ny] nodes of each list (static)
 };
 
 struct WallHeatPlan {
@@ -255,40 +303,15 @@ HF_HD inline void wall_heat_list(const WallHeatConst& K, int nx, int l, const in
 // Position of list l's k-th value in a row of 4 nx + ny entries.
 HF_HD inline int wall_heat_entry(int nx, int l, int k) { return l < nx ? k * nx + l : WALL_HEAT_X * nx + (l - nx); }
 
-// Ring and statistics -> WallHeatHistory, oldest first; time_of(t): the
-// reader's clock for a stored time.  stat: m, M, peak, peak_time [ne] each.
+// Ring and statistics -> WallHeatHistory, oldest first (sampled_history_fill).
 template <class TimeOf>
-inline WallHeatHistory wall_heat_history_from(const WallHeatPlan& P, const WallHeatOpts& o, const real* vals,
-                                              const double* times, long total, const double* stat,
-                                              const StatsScalars& sc, TimeOf time_of) {
+inline WallHeatHistory wall_heat_history_from(const WallHeatPlan& P, const WallHeatOpts& o, const SampledRing& r,
+                                              TimeOf time_of) {
   WallHeatHistory H;
   H.nx = P.nx;
   H.ny = P.ny;
-  H.total = total;
-  const long cap = o.capacity;
-  const size_t ne = (size_t)P.nentries();
-  const long n = cap ? std::min(total, cap) : 0, first = cap && total > cap ? total % cap : 0;
-  H.times.resize(n);
-  H.vals.resize((size_t)n * ne);
-  for (long k = 0; k < n; k++) {
-    const long s = (first + k) % cap;
-    H.times[k] = time_of(times[s]);
-    std::copy(vals + (size_t)s * ne, vals + (size_t)(s + 1) * ne, H.vals.begin() + (size_t)k * ne);
-  }
+  sampled_history_fill(H, r, o.capacity, (size_t)P.nentries(), o.statistics, time_of);
   for (int l = 0; l < P.nlists(); l++) (l < P.nx ? H.x_nodes : H.y_nodes).push_back(P.off[l + 1] - P.off[l]);
-  H.statistics = o.statistics;
-  if (o.statistics) {
-    H.time = sc.W;
-    H.samples = (long)sc.samples;
-    H.mean.assign(stat, stat + ne);
-    H.var.assign(stat + ne, stat + 2 * ne);
-    H.peak.assign(stat + 2 * ne, stat + 3 * ne);
-    H.peak_time.assign(ne, 0.0);
-    for (size_t k = 0; k < ne; k++) {
-      H.var[k] = sc.samples ? H.var[k] / sc.W : 0.0;
-      if (sc.samples) H.peak_time[k] = time_of(stat[3 * ne + k]);
-    }
-  }
   return H;
 }
 

@@ -63,6 +63,22 @@ struct DevBuf {
   }
 };
 
+// A device array that only grows: arming a recorder again, or a plan rebuilt
+// by upload(), uses what is there while it fits, so doing either over and over
+// does not grow device memory.  n == 0 allocates nothing.
+template <class T>
+struct DevArray {
+  T* p = nullptr;
+  size_t cap = 0;
+  // true: allocated (zero-filled by memsets of the null stream: synchronise before the solver stream uses it)
+  bool ensure(DevBuf& mem, size_t n) {
+    if (n <= cap) return false;
+    p = mem.alloc<T>(n);
+    cap = n;
+    return true;
+  }
+};
+
 struct DeviceSolver::Impl {
   DevBuf mem;
   hipStream_t stream = nullptr;
@@ -118,33 +134,69 @@ struct DeviceSolver::Impl {
   ScenarioTables* scen = nullptr;
   long* probe_idx = nullptr;   // K8 monitor probes (sample_monitors)
   real* probe_out = nullptr;
+  // The recorders: the argument block the kernels take, and behind it the
+  // arrays its pointers are set from (DevArray: arming again reuses what fits)
   ProbeRing ring{};            // per-step recorder (record_probes); cap == 0: not armed
+  struct {
+    DevArray<long> idx;
+    DevArray<real> rows;
+    DevArray<double> times;
+    DevArray<unsigned long long> count;
+  } ring_mem;
   LoadsDev loads{};            // per-step load recorder (record_loads); cap == 0: not armed
-  // ... its device arrays and their sizes (arming again or a plan rebuilt by upload reuses what fits)
-  long *loads_cell = nullptr, *loads_cell2 = nullptr, *loads_off = nullptr;
-  real *loads_coef = nullptr, *loads_scratch = nullptr, *loads_vals = nullptr;
-  uint8_t* loads_kind = nullptr;
-  double* loads_times = nullptr;
-  long loads_terms_cap = 0;
-  int loads_off_cap = 0;
-  size_t loads_vals_cap = 0, loads_times_cap = 0;
+  struct {
+    DevArray<long> cell, cell2, off;
+    DevArray<real> coef, scratch, vals;
+    DevArray<uint8_t> kind;
+    DevArray<double> times;
+    DevArray<unsigned long long> count;
+  } loads_mem;
+  struct SampleRingMem {   // the arrays behind a SampleRing
+    DevArray<real> vals;
+    DevArray<double> times, stat;
+    DevArray<WallHeatScalars> sc;
+  };
+  // A recorder's array of n entries, and a plan's host vector in one, while the
+  // stream is idle (the caller waits for the copies before the vector goes).
+  template <class T>
+  T* grown(DevArray<T>& a, size_t n) {
+    if (a.ensure(mem, n)) HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+    return a.p;
+  }
+  template <class T>
+  const T* plan_array(DevArray<T>& a, const std::vector<T>& v) {
+    grown(a, v.size());
+    if (!v.empty()) HIP_CHECK(hipMemcpyAsync(a.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+    return a.p;
+  }
+  // The sampled ring of the wall heat and the surface recorder: arrays for
+  // `cap` rows of `ne` entries behind r; ring and statistics empty with the
+  // clock at now (t_off: the solver's time_offset); both read back to the host
+  // (the last two in observe.hip, beside the kernels).
+  void ring_alloc(SampleRingMem& a, SampleRing& r, size_t ne, int cap) {
+    r.vals = grown(a.vals, (size_t)cap * ne);
+    r.times = grown(a.times, (size_t)cap);
+    r.stat = grown(a.stat, 4 * ne);
+    r.sc = grown(a.sc, 1);
+    r.cap = cap;
+  }
+  void ring_reset(const SampleRing& r, size_t ne, int every, bool step_weight, double t_off);
+  SampledRing ring_read(const SampleRing& r, size_t ne);
   WallHeatDev wallq{};         // per-step wall heat recorder (record_wall_heat)
-  // ... its device arrays and their sizes (arming again or a plan rebuilt by upload reuses what fits)
-  long* wallq_cells = nullptr;
-  int *wallq_node5 = nullptr, *wallq_off = nullptr, *wallq_list = nullptr;
-  real *wallq_scratch = nullptr, *wallq_vals = nullptr;
-  double *wallq_times = nullptr, *wallq_stat = nullptr;
-  long wallq_cells_cap = 0, wallq_nodes_cap = 0, wallq_list_cap = 0;
-  size_t wallq_vals_cap = 0, wallq_times_cap = 0;
+  struct {
+    DevArray<long> cells;
+    DevArray<int> node5, off, list;
+    DevArray<real> scratch;
+    SampleRingMem ring;
+  } wallq_mem;
   SurfaceDev surf{};           // per-step surface recorder (record_surface)
-  // ... its device arrays and their sizes (arming again or a plan rebuilt by upload reuses what fits)
-  long* surf_cells = nullptr;
-  uint8_t *surf_mask = nullptr, *surf_bits = nullptr;
-  int* surf_idx = nullptr;
-  real *surf_scratch = nullptr, *surf_vals = nullptr;
-  double *surf_times = nullptr, *surf_stat = nullptr;
-  long surf_cells_cap = 0, surf_nodes_cap = 0;
-  size_t surf_vals_cap = 0, surf_times_cap = 0, surf_stat_cap = 0;
+  struct {
+    DevArray<long> cells;
+    DevArray<uint8_t> mask, bits;
+    DevArray<int> idx;
+    DevArray<real> scratch;
+    SampleRingMem ring;
+  } surf_mem;
   FlowStats stats{};           // whole-field statistics (start_averaging)
   size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
   size_t stats_used = 0;       // of which the armed options use (stats_plane_count)
@@ -399,6 +451,25 @@ struct DeviceSolver::Impl {
     s.betas = betas;
     s.dSdxs = dSdxs[db];
     s.dSdys = dSdys[db];
+  }
+
+  // on_cycle_roll: the device's time_part restarts T lower, and every stored
+  // value of it moves with it: the n entries of a device array (none: nothing to do)
+  void shift_times(double* a, size_t n, double T) {
+    if (!n) return;
+    std::vector<double> t(n);
+    HIP_CHECK(hipMemcpyAsync(t.data(), a, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (double& x : t) x -= T;
+    HIP_CHECK(hipMemcpyAsync(a, t.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  // ... the offset of a tick's clock, time_part - t_off, which so goes on unbroken
+  void shift_clock(StatsScalars* sc, double T) { shift_times(&sc->t_off, 1, T); }
+  // ... and a sampled ring: its rows' times and its peak times (all set once a sample was taken)
+  void shift_ring(const SampleRing& r, size_t ne, double T) {
+    shift_times(r.times, (size_t)r.cap, T);
+    shift_times(r.stat + 3 * ne, ne, T);
   }
 };
 

@@ -18,7 +18,8 @@
 //                       (hf2d_lnm_*; lean_mech.hpp likewise)
 //   transport.hip       halo_kernels.hpp: halo pack / unpack, dt fold, xGMI
 //                       mailbox kernels (hf2d_p2p_*); RCCL and in-process transports
-//   observe.hip         monitors, probe_history.hpp (per-step recorder),
+//   observe.hip         monitors and the five per-step observers: probe_history.hpp,
+//                       load_history.hpp, wall_heat.hpp, surface_history.hpp (recorders),
 //                       flow_stats.hpp (time-averaged flow statistics)
 //   device_knobs.hpp    the tuning knobs, one row each: members, environment reads,
 //                       Python attributes and mode_signature() are expanded from it
@@ -432,29 +433,25 @@ void DeviceSolver::upload() {
   // the accumulator's clock is time_part - t_off, the host's cur_time_part:
   // it goes on from the host's value across the restart of time_part, and no
   // sample is weighted across an upload
+  // (the weights of the wall heat and the surface recorder likewise)
   const double st_clock[2] = {(double)cur_time_part, time_offset};
-  if (stats_armed) {
-    static_assert(offsetof(StatsScalars, t_seen) + sizeof(double) == offsetof(StatsScalars, t_off), "adjacent");
-    cp(&m.stats.sc->t_seen, st_clock, sizeof st_clock);
-  }
-  if (wallq_armed) cp(&m.wallq.sc->s.t_seen, st_clock, sizeof st_clock);   // (the wall heat recorder's weights likewise)
-  if (surf_armed) cp(&m.surf.sc->s.t_seen, st_clock, sizeof st_clock);     // (and the surface recorder's)
+  static_assert(offsetof(StatsScalars, t_seen) + sizeof(double) == offsetof(StatsScalars, t_off), "adjacent");
+  for (StatsScalars* t : tick_scalars()) cp(&t->t_seen, st_clock, sizeof st_clock);
   HIP_CHECK(hipStreamSynchronize(st));
   nstep = 0;
   abuf = 0;
   sbuf = 0;
   dsbuf = 0;
   pbuf = 0;
-  // (the records were replaced: the armed load recorder's cells follow their flags)
-  if (loads_cap) loads_plan_rebuild();
-  if (wallq_armed) wallq_plan_upload(wallq_plan_build(wallq_opts));   // (and the wall heat recorder's nodes)
-  if (surf_armed) {   // (and the surface recorder's; another node count restarts its ring and statistics)
-    SurfacePlan P = surf_plan_build(surf_opts);
-    const bool same = P.nnodes() == surf_plan.nnodes();
-    if (!same) surf_ring_alloc(P, m.surf.cap);
-    surf_plan_upload(std::move(P));
-    if (!same) surf_reset();
-  }
+  plans_rebuild();   // (the records were replaced: the armed recorders' cells follow their flags)
+}
+
+std::vector<StatsScalars*> DeviceSolver::tick_scalars() const {
+  std::vector<StatsScalars*> t;
+  if (stats_armed) t.push_back(impl->stats.sc);
+  if (wallq_armed) t.push_back(&impl->wallq.ring.sc->s);
+  if (surf_armed) t.push_back(&impl->surf.ring.sc->s);
+  return t;
 }
 
 void DeviceSolver::set_lean_plain(bool on) {
@@ -516,9 +513,10 @@ void DeviceSolver::download(Field& J) {
 // device's time_part restarts with it, so that the host's cur_time_part stays
 // the plain sum of this cycle's dt -- bit for bit the CPU stepper's -- and not
 // the difference of two running sums (one ulp off after the first cycle
-// boundary).  The two clocks derived from time_part move with it: the probe
-// recorder's stored times (probe_history() converts rows of earlier cycles as
-// before) and the accumulator's offset (its clock goes on unbroken).
+// boundary).  Everything derived from time_part moves with it: the times the
+// four rings and the peak-time planes store (host_time() converts those of
+// earlier cycles as before) and the offsets of the three ticks' clocks (which
+// go on unbroken).
 // Always called right after sync_scalars(), with no step in between:
 // last_dev_time is the device's time_part now.
 void DeviceSolver::on_cycle_roll() {
@@ -528,70 +526,12 @@ void DeviceSolver::on_cycle_roll() {
   const double T = last_dev_time;
   const double zero = 0.0;
   HIP_CHECK(hipMemcpyAsync(&m.sc->time_part, &zero, sizeof zero, hipMemcpyHostToDevice, m.stream));
-  if (probe_cap) {
-    std::vector<double> tp((size_t)m.ring.cap);
-    HIP_CHECK(hipMemcpyAsync(tp.data(), m.ring.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    for (double& t : tp) t -= T;
-    HIP_CHECK(hipMemcpyAsync(m.ring.times, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-  }
-  if (loads_cap) {
-    std::vector<double> tp((size_t)loads_cap);
-    HIP_CHECK(hipMemcpyAsync(tp.data(), m.loads.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    for (double& t : tp) t -= T;
-    HIP_CHECK(hipMemcpyAsync(m.loads.times, tp.data(), tp.size() * sizeof(double), hipMemcpyHostToDevice, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-  }
-  if (wallq_armed) {
-    // the ring's times and the peak times (all set once a sample was taken), and the weights' clock offset
-    const size_t ne = (size_t)wallq_plan.nentries();
-    std::vector<double> tp((size_t)m.wallq.cap + ne);
-    WallHeatScalars ws;
-    if (m.wallq.cap)
-      HIP_CHECK(hipMemcpyAsync(tp.data(), m.wallq.times, (size_t)m.wallq.cap * sizeof(double), hipMemcpyDeviceToHost,
-                               m.stream));
-    HIP_CHECK(hipMemcpyAsync(tp.data() + m.wallq.cap, m.wallq.stat + 3 * ne, ne * sizeof(double), hipMemcpyDeviceToHost,
-                             m.stream));
-    HIP_CHECK(hipMemcpyAsync(&ws, m.wallq.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    for (double& t : tp) t -= T;
-    ws.s.t_off -= T;
-    if (m.wallq.cap)
-      HIP_CHECK(hipMemcpyAsync(m.wallq.times, tp.data(), (size_t)m.wallq.cap * sizeof(double), hipMemcpyHostToDevice,
-                               m.stream));
-    HIP_CHECK(hipMemcpyAsync(m.wallq.stat + 3 * ne, tp.data() + m.wallq.cap, ne * sizeof(double), hipMemcpyHostToDevice,
-                             m.stream));
-    HIP_CHECK(hipMemcpyAsync(&m.wallq.sc->s.t_off, &ws.s.t_off, sizeof(double), hipMemcpyHostToDevice, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-  }
-  if (surf_armed) {
-    // likewise the surface recorder's ring times, peak times and clock offset
-    const size_t ne = (size_t)SURFACE_NVARS * surf_plan.nnodes();
-    std::vector<double> tp((size_t)m.surf.cap + ne);
-    WallHeatScalars ws;
-    auto mv = [&](void* d, const void* s, size_t bytes, hipMemcpyKind k) {
-      if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, k, m.stream));
-    };
-    mv(tp.data(), m.surf.times, (size_t)m.surf.cap * sizeof(double), hipMemcpyDeviceToHost);
-    mv(tp.data() + m.surf.cap, m.surf.stat + 3 * ne, ne * sizeof(double), hipMemcpyDeviceToHost);
-    mv(&ws, m.surf.sc, sizeof ws, hipMemcpyDeviceToHost);
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    for (double& t : tp) t -= T;
-    ws.s.t_off -= T;
-    mv(m.surf.times, tp.data(), (size_t)m.surf.cap * sizeof(double), hipMemcpyHostToDevice);
-    mv(m.surf.stat + 3 * ne, tp.data() + m.surf.cap, ne * sizeof(double), hipMemcpyHostToDevice);
-    mv(&m.surf.sc->s.t_off, &ws.s.t_off, sizeof(double), hipMemcpyHostToDevice);
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-  }
-  if (stats_armed) {
-    double off = 0.0;
-    HIP_CHECK(hipMemcpyAsync(&off, &m.stats.sc->t_off, sizeof off, hipMemcpyDeviceToHost, m.stream));
-    HIP_CHECK(hipStreamSynchronize(m.stream));
-    off -= T;
-    HIP_CHECK(hipMemcpyAsync(&m.stats.sc->t_off, &off, sizeof off, hipMemcpyHostToDevice, m.stream));
-  }
+  // (a paused recorder's rows are not of the trial steps' clock: autotune() ends in upload())
+  if (probes_live()) m.shift_times(m.ring.times, (size_t)m.ring.cap, T);
+  if (loads_live()) m.shift_times(m.loads.times, (size_t)m.loads.cap, T);
+  if (wallq_live()) m.shift_ring(m.wallq.ring, (size_t)wallq_plan.nentries(), T);
+  if (surf_live()) m.shift_ring(m.surf.ring, surf_plan.nentries(), T);
+  for (StatsScalars* t : tick_scalars()) m.shift_clock(t, T);
   HIP_CHECK(hipStreamSynchronize(m.stream));
   m.sc_host->time_part = 0.0;
   time_offset = 0.0;
@@ -703,17 +643,10 @@ uint64_t DeviceSolver::mode_signature() const {
 #undef HF2D_KNOB_MIX
   // and the state that is not a knob
   const int state[] = {lean_state, lns_state, sbuf, abuf, dsbuf, pbuf, cbuf, (int)(p2p_fuse && impl->p2p.on),
-                       // (a window captured before record_probes has no recorder launch, one
-                       // captured before arming again writes the previous ring)
-                       probe_gen,
-                       // (likewise the accumulator's two launches: start / stop_averaging)
-                       stats_gen,
-                       // (and the load recorder's: record_loads, a plan rebuilt by upload)
-                       loads_gen,
-                       // (and the wall heat recorder's: record_wall_heat, a plan rebuilt by upload)
-                       wallq_gen,
-                       // (and the surface recorder's: record_surface, a plan rebuilt by upload)
-                       surf_gen};
+                       // (a window captured before an observer was armed has none of its launches,
+                       // one captured before it was armed again, stopped, or its plan rebuilt by
+                       // upload holds the previous arguments)
+                       observers_gen};
   for (int f : state) mix(f);
   return h;
 }
@@ -895,11 +828,14 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   if (!done.exchanged && (m.comm || m.local || m.p2p.on) && m.nranks > 1)
     exchange(lns_state ? CpuSolver::HALO_LNS : lean_state ? CpuSolver::HALO_LEAN : CpuSolver::HALO_STATE, c.slot_next);
   if (!cs.cfg.isAdiabaticWall) wall_heat(c);
-  if (probe_cap) launch_probe_record(P);
-  if (stats_on) launch_stats(P);
-  if (loads_cap) launch_loads(P, c.slot, c.slot_next);
-  if (wallq_armed) launch_wall_heat(P, c.slot, c.slot_next);
-  if (surf_armed) launch_surface(P, c.slot, c.slot_next);
+  if (probes_live() || stats_live() || loads_live() || wallq_live() || surf_live()) {
+    const PostStep v = post_step(c.slot, c.slot_next);
+    if (probes_live()) launch_probe_record(P, v);
+    if (stats_live()) launch_stats(P, v);
+    if (loads_live()) launch_loads(P, v);
+    if (wallq_live()) launch_wall_heat(P, v);
+    if (surf_live()) launch_surface(P, v);
+  }
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;
   StepResult r;
@@ -943,16 +879,7 @@ std::string DeviceSolver::autotune(int steps) {
   const bool s_src = isSrcAdd, s_out = step_outputs;
   const ResidualSummary s_res = last_res;
   const bool s_resv = last_res_valid;
-  const long s_probe = probe_cap;   // the trial steps are not the run's: an armed recorder sits them out
-  probe_cap = 0;
-  const bool s_stats = stats_on;   // (nor does the accumulator take them as samples)
-  stats_on = false;
-  const long s_loads = loads_cap;  // (nor the load recorder)
-  loads_cap = 0;
-  const bool s_wallq = wallq_armed;   // (nor the wall heat recorder)
-  wallq_armed = false;
-  const bool s_surf = surf_armed;     // (nor the surface recorder)
-  surf_armed = false;
+  observers_paused = true;   // the trial steps are not the run's: the armed observers sit them out
   struct Cand {
     int cpt, tj, nt, wgcu = 0;
   };
@@ -1081,11 +1008,7 @@ std::string DeviceSolver::autotune(int steps) {
   step_outputs = s_out;
   last_res = s_res;
   last_res_valid = s_resv;
-  probe_cap = s_probe;
-  stats_on = s_stats;
-  loads_cap = s_loads;
-  wallq_armed = s_wallq;
-  surf_armed = s_surf;
+  observers_paused = false;
   upload();   // device scalars from the restored host state
   graph_launches = 0;
   lns_steps = lnm_steps = 0;   // (the tuning steps do not count as the run's)

@@ -18,6 +18,7 @@ namespace hf2d {
 
 struct LnmArrays;
 struct LeanTile;
+struct PostStep;
 
 bool gpu_available();
 // Largest number of slots per thread that the single-gas lean tile kernel of
@@ -260,7 +261,14 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   unsigned long long* tile_trace = nullptr;   // set only inside trace_tile
   std::vector<long> probe_idx_host;
   std::vector<real> probe_buf_host;
-  int probe_gen = 0;            // arming generation (mode_signature: a cached window bakes the ring in)
+  // The five observers.  Armed: the plan and the arrays exist.  A cached graph
+  // window bakes an observer's launches and arrays in, so arming, re-arming,
+  // stopping or a plan rebuilt by upload() bumps observers_gen
+  // (mode_signature: no window captured before replays after).  autotune()'s
+  // trial steps are not the run's: while observers_paused, an armed observer
+  // sits them out -- no launch, and nothing the step does for a recorder.
+  int observers_gen = 0;
+  bool observers_paused = false;
   long probe_cap = 0;           // 0: not armed
   std::vector<long> probe_rec_idx;   // local cell of each probe (-1: another strip's column)
   bool stats_on = false;        // the two kernels are launched
@@ -268,24 +276,26 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   bool stats_second = false;
   bool stats_favre = false;
   std::vector<int> stats_species;   // mechanism indices of the listed species
-  int stats_gen = 0;            // arming generation (mode_signature, as probe_gen)
-  int loads_gen = 0;            // arming generation (mode_signature, as probe_gen)
   long loads_cap = 0;           // 0: not armed
   bool loads_friction = false;  // the armed plan holds friction terms: the split fills store their gradients every step
   LoadPlan loads_plan;          // host copy of the armed plan
   std::vector<LoadBox> loads_boxes;
   std::vector<LoadCut> loads_cuts;
-  int wallq_gen = 0;            // arming generation (mode_signature, as probe_gen)
   bool wallq_armed = false;
   WallHeatOpts wallq_opts;      // what the plan is rebuilt from
   WallHeatPlan wallq_plan;      // host copy of the armed plan
-  int surf_gen = 0;             // arming generation (mode_signature, as probe_gen)
   bool surf_armed = false;
   bool surf_friction = false;   // the armed plan holds friction terms (as loads_friction)
   SurfaceOpts surf_opts;        // what the plan is rebuilt from
   SurfacePlan surf_plan;        // host copy of the armed plan
+  // armed and not paused: the step launches the observer
+  bool probes_live() const { return probe_cap > 0 && !observers_paused; }
+  bool stats_live() const { return stats_on && !observers_paused; }
+  bool loads_live() const { return loads_cap > 0 && !observers_paused; }
+  bool wallq_live() const { return wallq_armed && !observers_paused; }
+  bool surf_live() const { return surf_armed && !observers_paused; }
   // the split fills store their gradients every step while a recorder reads them
-  bool friction_recorded() const { return (loads_cap > 0 && loads_friction) || (surf_armed && surf_friction); }
+  bool friction_recorded() const { return (loads_live() && loads_friction) || (surf_live() && surf_friction); }
   bool fx_pending = false;   // fused tile steps left the newest ghost columns and dt in the mailbox (p2p_complete)
   // fused lean N-S steps: the last step's halo is still in the mailbox; the
   // next fused step's edge tiles unpack it (lns_ghost_prologue)
@@ -304,23 +314,29 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   std::unique_ptr<GraphCache> graph;
   std::vector<StepParams> pending;
   void run_graph();
-  void launch_probe_record(const StepParams& P);   // end of do_step_eager, post-step buffers
-  void launch_stats(const StepParams& P);          // after it
-  void launch_loads(const StepParams& P, int slot, int slot_next);   // the load recorder's two launches
-  LoadPlan loads_plan_build(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts) const;
-  void loads_plan_upload(LoadPlan&& P);            // a built plan -> device
-  void loads_plan_rebuild();                       // the armed boxes / cuts over the records upload() replaced
-  void launch_wall_heat(const StepParams& P, int slot, int slot_next);   // the wall heat recorder's three launches
-  WallHeatPlan wallq_plan_build(const WallHeatOpts& o) const;
-  void wallq_plan_upload(WallHeatPlan&& P);        // a built plan -> device
-  void wallq_reset();                              // ring and statistics empty, the clock at now
-  void launch_surface(const StepParams& P, int slot, int slot_next);   // the surface recorder's three launches
-  SurfacePlan surf_plan_build(const SurfaceOpts& o) const;
-  void surf_plan_upload(SurfacePlan&& P);          // a built plan -> device
-  void surf_ring_alloc(const SurfacePlan& P, int cap);   // ring and statistics arrays for the plan's node count
-  void surf_reset();                               // ring and statistics empty, the clock at now
+  // The observers' launches at the end of do_step_eager, in this order, each
+  // over the one PostStep of the step; nothing in them allocates, copies or
+  // synchronises.
+  PostStep post_step(int slot, int slot_next) const;
+  void launch_probe_record(const StepParams& P, const PostStep& v);
+  void launch_stats(const StepParams& P, const PostStep& v);
+  void launch_loads(const StepParams& P, const PostStep& v);       // the load recorder's two launches
+  void launch_wall_heat(const StepParams& P, const PostStep& v);   // the wall heat recorder's three launches
+  void launch_surface(const StepParams& P, const PostStep& v);     // the surface recorder's three launches
   void lns_fill_views(SoA& sin, SoA& out) const;   // the views lns_materialize's fill would run over now
-  int post_step_view(SoA& s) const;                // PR_* kind and view both of them read
+  int post_step_view(SoA& s) const;                // PR_* kind and view of the post-step buffers
+  // A recorder's plan over the records the backend holds now (throws where a
+  // value could not be recorded exactly), and a built plan into the device arrays.
+  LoadPlan loads_plan_build(const std::vector<LoadBox>& boxes, const std::vector<LoadCut>& cuts) const;
+  void loads_plan_upload(LoadPlan&& P);
+  WallHeatPlan wallq_plan_build(const WallHeatOpts& o) const;
+  void wallq_plan_upload(WallHeatPlan&& P);
+  SurfacePlan surf_plan_build(const SurfaceOpts& o) const;
+  void surf_plan_upload(SurfacePlan&& P);
+  void refuse_wall_nodes(const std::string& who, const char* nodes, bool wall_T) const;   // the two rules that refuse such a plan
+  void plans_rebuild();                   // upload() replaced the records under the armed recorders
+  double host_time(double t_dev) const;   // the host's time of a stored DevScalars::time_part
+  std::vector<StatsScalars*> tick_scalars() const;   // device scalars of every armed tick: accumulator, wall heat, surface
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)
   // One step (do_step_eager): the kernels that run it, what every path reads
   // of the step, and what a path reports to the common tail.

@@ -92,17 +92,17 @@ void DeviceSolver::record_probes(const std::vector<std::pair<int, int>>& cells, 
   ProbeRing r;
   r.n = n;
   r.cap = (int)std::min<long>(capacity, 0x7fffffffL);
-  long* idx = m.mem.alloc<long>(n);
-  r.idx = idx;
-  r.rows = m.mem.alloc<real>((size_t)r.cap * n * PROBE_VARS);
-  r.times = m.mem.alloc<double>((size_t)r.cap);
-  r.count = m.mem.alloc<unsigned long long>(1);
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
-  HIP_CHECK(hipMemcpyAsync(idx, probe_rec_idx.data(), n * sizeof(long), hipMemcpyHostToDevice, m.stream));
+  HIP_CHECK(hipDeviceSynchronize());   // (the steps flush_pending launched: nothing in flight reads the arrays)
+  auto& a = m.ring_mem;
+  r.idx = m.plan_array(a.idx, probe_rec_idx);
+  r.rows = m.grown(a.rows, (size_t)r.cap * n * PROBE_VARS);
+  r.times = m.grown(a.times, (size_t)r.cap);
+  r.count = m.grown(a.count, 1);
+  HIP_CHECK(hipMemsetAsync(r.count, 0, sizeof(unsigned long long), m.stream));
   HIP_CHECK(hipStreamSynchronize(m.stream));
   m.ring = r;
   probe_cap = r.cap;
-  probe_gen++;   // windows captured so far must not replay (mode_signature)
+  observers_gen++;
 }
 
 void DeviceSolver::clear_probe_history() {
@@ -129,21 +129,19 @@ ProbeHistory DeviceSolver::probe_history() {
   ProbeHistory H;
   H.nprobes = r.n;
   H.total = (long)total;
-  const long cap = r.cap, n = std::min<long>(H.total, cap), first = H.total > cap ? H.total % cap : 0;
-  H.times.resize(n);
-  H.values.resize((size_t)n * row);
-  for (long k = 0; k < n; k++) {
-    const long s = (first + k) % cap;
-    // the device accumulates time since the cycle start (on_cycle_roll moved
-    // the rows of earlier cycles with it); the host's time is
-    // global_time + (time_part - time_offset) (sync_scalars, summary)
-    const real part = tp[s] - time_offset;
-    H.times[k] = cs.global_time + part;
-    std::copy(rows.begin() + s * row, rows.begin() + (s + 1) * row, H.values.begin() + k * row);
-  }
+  ring_oldest_first(rows.data(), row, tp.data(), H.total, (long)r.cap, [&](double t) { return host_time(t); },
+                    H.values, H.times);
   H.owned.resize(r.n);
   for (int q = 0; q < r.n; q++) H.owned[q] = probe_rec_idx[q] >= 0 ? 1 : 0;
   return H;
+}
+
+// The device accumulates time since the cycle start (on_cycle_roll moved the
+// stored times of earlier cycles with it); the host's time is
+// global_time + (time_part - time_offset) (sync_scalars, summary).
+double DeviceSolver::host_time(double t_dev) const {
+  const real part = t_dev - time_offset;
+  return (double)(cs.global_time + part);
 }
 
 // Last launch of a step: the row of every probe from the post-step buffers,
@@ -183,18 +181,26 @@ int DeviceSolver::post_step_view(SoA& s) const {
   return kind;
 }
 
-void DeviceSolver::launch_probe_record(const StepParams& P) {
-  Impl& m = *impl;
-  SoA s;
-  const int kind = post_step_view(s);
-  const dim3 g(1), b(PROBE_MAX);
-  switch (kind) {
-    case PR_SGL: hipLaunchKernelGGL(hf2d_probe_record<PR_SGL>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
-    case PR_SGT: hipLaunchKernelGGL(hf2d_probe_record<PR_SGT>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
-    case PR_MECH: hipLaunchKernelGGL(hf2d_probe_record<PR_MECH>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
-    case PR_LEAN: hipLaunchKernelGGL(hf2d_probe_record<PR_LEAN>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
-    default: hipLaunchKernelGGL(hf2d_probe_record<PR_GATHER>, g, b, 0, m.stream, P, s, m.ring, m.sc); break;
+// ... and with it, for the lean N-S / mechanism state, the views and the dt
+// slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3,
+// else (nstep + 2) % 3).  Once per step, for every observer that is armed.
+PostStep DeviceSolver::post_step(int slot, int slot_next) const {
+  PostStep v;
+  v.kind = post_step_view(v.s);
+  v.fin = v.out = v.s;
+  v.fslot = slot;
+  if (lns_state) {
+    lns_fill_views(v.fin, v.out);
+    if (v.kind == PR_SGL) v.fslot = slot_next;
   }
+  return v;
+}
+
+void DeviceSolver::launch_probe_record(const StepParams& P, const PostStep& v) {
+  Impl& m = *impl;
+  with_kind(v.kind, [&](auto K) {
+    hipLaunchKernelGGL(hf2d_probe_record<decltype(K)::value>, dim3(1), dim3(PROBE_MAX), 0, m.stream, P, v.s, m.ring, m.sc);
+  });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -211,26 +217,17 @@ void DeviceSolver::record_loads(const std::vector<LoadBox>& boxes, const std::ve
   // its boxes, cuts, plan and ring are replaced only together, below)
   LoadPlan P = loads_plan_build(boxes, cuts);
   const int cap = (int)std::min<long>(capacity, 0x7fffffffL);
-  const size_t nv = (size_t)cap * P.nlists();
   LoadsDev& L = m.loads;
-  // (arrays that are large enough are used again: arming over and over does not grow device memory)
-  if (nv > m.loads_vals_cap) {
-    m.loads_vals = m.mem.alloc<real>(nv);
-    m.loads_vals_cap = nv;
-  }
-  if ((size_t)cap > m.loads_times_cap) {
-    m.loads_times = m.mem.alloc<double>((size_t)cap);
-    m.loads_times_cap = (size_t)cap;
-  }
-  if (!L.count) L.count = m.mem.alloc<unsigned long long>(1);
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  auto& a = m.loads_mem;
+  HIP_CHECK(hipDeviceSynchronize());   // (the steps flush_pending launched: nothing in flight reads the arrays)
   loads_cap = 0;
+  L.vals = m.grown(a.vals, (size_t)cap * P.nlists());
+  L.times = m.grown(a.times, (size_t)cap);
+  L.count = m.grown(a.count, 1);
+  L.cap = cap;
   loads_plan_upload(std::move(P));
   loads_boxes = boxes;
   loads_cuts = cuts;
-  L.vals = m.loads_vals;
-  L.times = m.loads_times;
-  L.cap = cap;
   HIP_CHECK(hipMemsetAsync(L.count, 0, sizeof(unsigned long long), m.stream));
   HIP_CHECK(hipStreamSynchronize(m.stream));
   loads_cap = cap;
@@ -244,6 +241,14 @@ LoadPlan DeviceSolver::loads_plan_build(const std::vector<LoadBox>& boxes, const
     if (c < 0 || c >= h.N) throw std::runtime_error("load recorder: a term's cell lies outside the solver's arrays");
   for (long c : P.cell2)
     if (c < 0 || c >= h.N) throw std::runtime_error("load recorder: a term's cell lies outside the solver's arrays");
+  // (the box terms are the wall nodes', and they read no wall temperature)
+  if (P.off[(size_t)LOAD_PARTS * P.nboxes] > 0) refuse_wall_nodes("load recorder", "wall terms", false);
+  return P;
+}
+
+// The two rules that refuse a plan with wall nodes, in the words of the
+// recorder `who`, which calls them `nodes`; wall_T: it reads their temperature.
+void DeviceSolver::refuse_wall_nodes(const std::string& who, const char* nodes, bool wall_T) const {
   // the lean N-S / mechanism kinds fill a wall node with the parameters of the
   // recorded step; the fill a download runs takes the next step's, whose
   // is_mu_t differs after the last step before TurbStartIter.  That step is a
@@ -254,59 +259,37 @@ LoadPlan DeviceSolver::loads_plan_build(const std::vector<LoadBox>& boxes, const
   // holds for every later step; upload() asks again for the plan it rebuilds.
   // (the lean mechanism state exists for at most LNM_NSB = 9 species, the
   // block loads_wall_fill runs the fill with: lnm_ok)
-  const bool box_terms = P.off[(size_t)LOAD_PARTS * P.nboxes] > 0;
-  if (box_terms && (lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset &&
-      cs.cfg.TurbStartIter >= 2 && last_iter + iter < (long)cs.cfg.TurbStartIter)
-    throw std::runtime_error("load recorder: wall terms on the lean N-S / mechanism state cannot be recorded exactly "
-                             "before TurbStartIter has passed; arm (or upload) later");
-  return P;
+  if ((lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset && cs.cfg.TurbStartIter >= 2 &&
+      last_iter + iter < (long)cs.cfg.TurbStartIter)
+    throw std::runtime_error(who + ": " + nodes + " on the lean N-S / mechanism state cannot be recorded exactly before "
+                                                  "TurbStartIter has passed; arm (or upload) later");
+  // a plain lean tile step stores no T, and T = p / R / rho holds only where R
+  // does not change over the step; the tile kernel runs its output variant for
+  // the probe recorder and the accumulator alone (step_tile.hip)
+  if (wall_T && lean_ok && !lean_sg_ok && make_params(last_iter + iter).chem_model != NO_REACTIONS)
+    throw std::runtime_error(who + ": a reacting gas mixture on the lean inviscid step stores no wall temperature between "
+                                   "outputs; the recorder cannot be armed on this deck");
 }
 
 // A built plan into the device arrays (used again where they are large
 // enough; the stream is idle: flush_pending / upload synchronised it).
 void DeviceSolver::loads_plan_upload(LoadPlan&& P) {
   Impl& m = *impl;
-  const long nt = P.nterms();
-  const int nl = P.nlists();
-  if (nt > m.loads_terms_cap) {
-    m.loads_cell = m.mem.alloc<long>((size_t)nt);
-    m.loads_cell2 = m.mem.alloc<long>((size_t)nt);
-    m.loads_coef = m.mem.alloc<real>((size_t)nt);
-    m.loads_kind = m.mem.alloc<uint8_t>((size_t)nt);
-    m.loads_scratch = m.mem.alloc<real>((size_t)nt);
-    m.loads_terms_cap = nt;
-  }
-  if (nl + 1 > m.loads_off_cap) {
-    m.loads_off = m.mem.alloc<long>((size_t)nl + 1);
-    m.loads_off_cap = nl + 1;
-  }
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets, and nothing in flight reads the arrays)
-  auto cp = [&](void* d, const void* s, size_t bytes) {
-    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, m.stream));
-  };
-  cp(m.loads_cell, P.cell.data(), nt * sizeof(long));
-  cp(m.loads_cell2, P.cell2.data(), nt * sizeof(long));
-  cp(m.loads_coef, P.coef.data(), nt * sizeof(real));
-  cp(m.loads_kind, P.kind.data(), nt * sizeof(uint8_t));
-  cp(m.loads_off, P.off.data(), ((size_t)nl + 1) * sizeof(long));
-  HIP_CHECK(hipStreamSynchronize(m.stream));
+  auto& a = m.loads_mem;
   LoadsDev& L = m.loads;
-  L.cell = m.loads_cell;
-  L.cell2 = m.loads_cell2;
-  L.coef = m.loads_coef;
-  L.kind = m.loads_kind;
-  L.off = m.loads_off;
-  L.scratch = m.loads_scratch;
-  L.nterms = nt;
-  L.nlists = nl;
+  L.nterms = P.nterms();
+  L.nlists = P.nlists();
+  L.scratch = m.grown(a.scratch, (size_t)L.nterms);
+  L.cell = m.plan_array(a.cell, P.cell);
+  L.cell2 = m.plan_array(a.cell2, P.cell2);
+  L.coef = m.plan_array(a.coef, P.coef);
+  L.kind = m.plan_array(a.kind, P.kind);
+  L.off = m.plan_array(a.off, P.off);
+  HIP_CHECK(hipStreamSynchronize(m.stream));
   loads_plan = std::move(P);
   loads_friction = loads_plan.friction();
-  loads_gen++;   // windows captured so far must not replay (mode_signature)
+  observers_gen++;
 }
-
-// upload() replaced the records under an armed recorder: the same boxes and
-// cuts over the new flags (as many lists as before: the ring keeps its shape).
-void DeviceSolver::loads_plan_rebuild() { loads_plan_upload(loads_plan_build(loads_boxes, loads_cuts)); }
 
 void DeviceSolver::clear_load_history() {
   if (!loads_cap) return;
@@ -330,11 +313,8 @@ LoadHistory DeviceSolver::load_history() {
     HIP_CHECK(hipMemcpyAsync(vals.data(), L.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
   HIP_CHECK(hipMemcpyAsync(tp.data(), L.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
   HIP_CHECK(hipStreamSynchronize(m.stream));
-  // (the probe ring's clock: probe_history)
-  return load_history_from_ring(loads_plan, vals.data(), (long)total, (long)L.cap, [&](long s) {
-    const real part = tp[s] - time_offset;
-    return (double)(cs.global_time + part);
-  });
+  return load_history_from_ring(loads_plan, vals.data(), tp.data(), (long)total, (long)L.cap,
+                                [&](double t) { return host_time(t); });
 }
 
 // The views the fill of lns_materialize would run over now (its sin == pold
@@ -361,33 +341,55 @@ void DeviceSolver::lns_fill_views(SoA& sin, SoA& out) const {
   out = m.view(h, sbuf, abuf, dsbuf, pbuf);
 }
 
-// After the other observers' launches; the same view, and for the lean N-S /
-// mechanism state the materialise fill's.  Nothing here allocates, copies or
-// synchronises.
-void DeviceSolver::launch_loads(const StepParams& P, int slot, int slot_next) {
+// (no term kernel of the PR_LEAN kind: a term reads no T, and the lean inviscid
+// arrays store everything else per cell, load_history.hpp)
+void DeviceSolver::launch_loads(const StepParams& P, const PostStep& v) {
   Impl& m = *impl;
-  SoA s;
-  const int kind = post_step_view(s);
-  SoA fin = s, out = s;
-  // the dt slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3, else (nstep + 2) % 3)
-  int fslot = slot;
-  if (lns_state) {
-    lns_fill_views(fin, out);
-    if (kind == PR_SGL) fslot = slot_next;
-  }
   const LoadsDev& L = m.loads;
   if (L.nterms > 0) {
     const dim3 g((unsigned)((L.nterms + LOADS_BLOCK - 1) / LOADS_BLOCK)), b(LOADS_BLOCK);
-    switch (kind) {
-      case PR_SGL: hipLaunchKernelGGL(hf2d_loads_terms<PR_SGL>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_SGT: hipLaunchKernelGGL(hf2d_loads_terms<PR_SGT>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_MECH: hipLaunchKernelGGL(hf2d_loads_terms<PR_MECH>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      default: hipLaunchKernelGGL(hf2d_loads_terms<PR_GATHER>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-    }
+    with_kind<false>(v.kind, [&](auto K) {
+      hipLaunchKernelGGL(hf2d_loads_terms<decltype(K)::value>, g, b, 0, m.stream, P, v.s, v.fin, v.out, L, m.sc, v.fslot);
+    });
     HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(hf2d_loads_fold, dim3(1), dim3(LOADS_FOLD_WAVES * WAVE), 0, m.stream, L, m.sc);
   HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// The sampled ring of the wall heat and the surface recorder (SampleRing)
+// ---------------------------------------------------------------------------
+// An empty ring and empty statistics whose clock starts at the present value.
+void DeviceSolver::Impl::ring_reset(const SampleRing& r, size_t ne, int every, bool step_weight, double t_off) {
+  WallHeatScalars s0{};
+  s0.s.every = every;
+  s0.s.step_weight = step_weight ? 1 : 0;
+  s0.s.t_off = t_off;
+  HIP_CHECK(hipMemcpyAsync(r.sc, &s0, sizeof s0, hipMemcpyHostToDevice, stream));
+  if (ne) HIP_CHECK(hipMemsetAsync(r.stat, 0, 4 * ne * sizeof(double), stream));
+  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, stream, &r.sc->s, sc);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+SampledRing DeviceSolver::Impl::ring_read(const SampleRing& r, size_t ne) {
+  SampledRing R;
+  WallHeatScalars ws;
+  R.vals.resize((size_t)r.cap * ne);
+  R.times.resize((size_t)r.cap);
+  R.stat.resize(4 * ne);
+  auto get = [&](void* d, const void* s, size_t bytes) {
+    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, stream));
+  };
+  get(&ws, r.sc, sizeof ws);
+  get(R.vals.data(), r.vals, R.vals.size() * sizeof(real));
+  get(R.times.data(), r.times, R.times.size() * sizeof(double));
+  get(R.stat.data(), r.stat, R.stat.size() * sizeof(double));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  R.sc = ws.s;
+  R.total = (long)ws.s.samples;
+  return R;
 }
 
 // ---------------------------------------------------------------------------
@@ -402,31 +404,15 @@ void DeviceSolver::record_wall_heat(const WallHeatOpts& o) {
   // (a refused plan throws here and leaves the armed recorder, if any, whole:
   // its options, plan, ring and statistics are replaced only together, below)
   WallHeatPlan P = wallq_plan_build(o);
-  const int cap = (int)std::min<long>(o.capacity, 0x7fffffffL);
-  const size_t ne = (size_t)P.nentries(), nv = (size_t)cap * ne;
-  WallHeatDev& L = m.wallq;
-  // (arrays that are large enough are used again: arming over and over does not grow device memory)
-  if (nv > m.wallq_vals_cap) {
-    m.wallq_vals = m.mem.alloc<real>(nv);
-    m.wallq_vals_cap = nv;
-  }
-  if ((size_t)cap > m.wallq_times_cap) {
-    m.wallq_times = m.mem.alloc<double>((size_t)cap);
-    m.wallq_times_cap = (size_t)cap;
-  }
-  if (!m.wallq_stat) m.wallq_stat = m.mem.alloc<double>(4 * ne);   // (nx, ny never change)
-  if (!L.sc) L.sc = m.mem.alloc<WallHeatScalars>(1);
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  HIP_CHECK(hipDeviceSynchronize());   // (the steps flush_pending launched: nothing in flight reads the arrays)
   wallq_armed = false;
+  SampleRing& r = m.wallq.ring;
+  m.ring_alloc(m.wallq_mem.ring, r, (size_t)P.nentries(), (int)std::min<long>(o.capacity, 0x7fffffffL));
+  r.statistics = o.statistics ? 1 : 0;
   wallq_plan_upload(std::move(P));
   wallq_opts = o;
-  wallq_opts.capacity = cap;
-  L.vals = m.wallq_vals;
-  L.times = m.wallq_times;
-  L.stat = m.wallq_stat;
-  L.cap = cap;
-  L.statistics = o.statistics ? 1 : 0;
-  wallq_reset();
+  wallq_opts.capacity = r.cap;
+  m.ring_reset(r, (size_t)wallq_plan.nentries(), o.every, o.step_weight, time_offset);
   wallq_armed = true;
 }
 
@@ -436,20 +422,7 @@ WallHeatPlan DeviceSolver::wallq_plan_build(const WallHeatOpts& o) const {
   WallHeatPlan P = build_wall_heat_plan(cs, cs.J, o, l_off);
   for (long c : P.cells)
     if (c < 0 || c >= h.N) throw std::runtime_error("wall heat recorder: a needed cell lies outside the solver's arrays");
-  // the lean N-S / mechanism kinds fill a needed cell with the parameters of
-  // the recorded step; the fill a download runs takes the next step's, whose
-  // is_mu_t differs after the last step before TurbStartIter (the load
-  // recorder's refusal, loads_plan_build, and its reasoning)
-  if (P.nnodes() > 0 && (lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset &&
-      cs.cfg.TurbStartIter >= 2 && last_iter + iter < (long)cs.cfg.TurbStartIter)
-    throw std::runtime_error("wall heat recorder: wall nodes on the lean N-S / mechanism state cannot be recorded "
-                             "exactly before TurbStartIter has passed; arm (or upload) later");
-  // a plain lean tile step stores no T, and T = p / R / rho holds only where R
-  // does not change over the step; the tile kernel runs its output variant for
-  // the probe recorder and the accumulator alone (step_tile.hip)
-  if (P.nnodes() > 0 && lean_ok && !lean_sg_ok && make_params(last_iter + iter).chem_model != NO_REACTIONS)
-    throw std::runtime_error("wall heat recorder: a reacting gas mixture on the lean inviscid step stores no wall "
-                             "temperature between outputs; the recorder cannot be armed on this deck");
+  if (P.nnodes() > 0) refuse_wall_nodes("wall heat recorder", "wall nodes", true);
   return P;
 }
 
@@ -457,117 +430,47 @@ WallHeatPlan DeviceSolver::wallq_plan_build(const WallHeatOpts& o) const {
 // enough; the stream is idle: flush_pending / upload synchronised it).
 void DeviceSolver::wallq_plan_upload(WallHeatPlan&& P) {
   Impl& m = *impl;
-  const long nc = P.ncells(), nn = P.nnodes(), nl = (long)P.list.size();
-  const int no = P.nlists() + 1;
-  if (nc > m.wallq_cells_cap) {
-    m.wallq_cells = m.mem.alloc<long>((size_t)nc);
-    m.wallq_scratch = m.mem.alloc<real>(3 * (size_t)nc);
-    m.wallq_cells_cap = nc;
-  }
-  if (nn > m.wallq_nodes_cap) {
-    m.wallq_node5 = m.mem.alloc<int>(5 * (size_t)nn);
-    m.wallq_nodes_cap = nn;
-  }
-  if (nl > m.wallq_list_cap) {
-    m.wallq_list = m.mem.alloc<int>((size_t)nl);
-    m.wallq_list_cap = nl;
-  }
-  if (!m.wallq_off) m.wallq_off = m.mem.alloc<int>((size_t)no);   // (nx + ny + 1: never changes)
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets, and nothing in flight reads the arrays)
-  auto cp = [&](void* d, const void* s, size_t bytes) {
-    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, m.stream));
-  };
-  cp(m.wallq_cells, P.cells.data(), nc * sizeof(long));
-  cp(m.wallq_node5, P.node5.data(), 5 * nn * sizeof(int));
-  cp(m.wallq_list, P.list.data(), nl * sizeof(int));
-  cp(m.wallq_off, P.off.data(), (size_t)no * sizeof(int));
-  HIP_CHECK(hipStreamSynchronize(m.stream));
+  auto& a = m.wallq_mem;
   WallHeatDev& L = m.wallq;
   L.K = P.K;
-  L.cells = m.wallq_cells;
-  L.node5 = m.wallq_node5;
-  L.list = m.wallq_list;
-  L.off = m.wallq_off;
-  L.scratch = m.wallq_scratch;
-  L.ncells = nc;
+  L.ncells = P.ncells();
   L.nx = P.nx;
   L.ny = P.ny;
-  wallq_plan = std::move(P);
-  wallq_gen++;   // windows captured so far must not replay (mode_signature)
-}
-
-// An empty ring and empty statistics whose clock starts at the present value.
-void DeviceSolver::wallq_reset() {
-  Impl& m = *impl;
-  WallHeatScalars s0{};
-  s0.s.every = wallq_opts.every;
-  s0.s.step_weight = wallq_opts.step_weight ? 1 : 0;
-  s0.s.t_off = time_offset;
-  HIP_CHECK(hipMemcpyAsync(m.wallq.sc, &s0, sizeof s0, hipMemcpyHostToDevice, m.stream));
-  HIP_CHECK(hipMemsetAsync(m.wallq.stat, 0, 4 * (size_t)wallq_plan.nentries() * sizeof(double), m.stream));
-  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, &m.wallq.sc->s, m.sc);
-  HIP_CHECK(hipGetLastError());
+  L.scratch = m.grown(a.scratch, 3 * (size_t)L.ncells);
+  L.cells = m.plan_array(a.cells, P.cells);
+  L.node5 = m.plan_array(a.node5, P.node5);
+  L.list = m.plan_array(a.list, P.list);
+  L.off = m.plan_array(a.off, P.off);
   HIP_CHECK(hipStreamSynchronize(m.stream));
+  wallq_plan = std::move(P);
+  observers_gen++;
 }
 
 void DeviceSolver::clear_wall_heat() {
   if (!wallq_armed) return;
   flush_pending();
   HIP_CHECK(hipSetDevice(dev));
-  wallq_reset();
+  impl->ring_reset(impl->wallq.ring, (size_t)wallq_plan.nentries(), wallq_opts.every, wallq_opts.step_weight, time_offset);
 }
 
 WallHeatHistory DeviceSolver::wall_heat_history() {
   if (!wallq_armed) throw std::runtime_error("wall_heat_history: no recorder armed (record_wall_heat)");
   flush_pending();
   HIP_CHECK(hipSetDevice(dev));
-  Impl& m = *impl;
-  const WallHeatDev& L = m.wallq;
-  const size_t ne = (size_t)wallq_plan.nentries();
-  WallHeatScalars ws;
-  std::vector<real> vals((size_t)L.cap * ne);
-  std::vector<double> tp((size_t)L.cap), stat(4 * ne);
-  HIP_CHECK(hipMemcpyAsync(&ws, L.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
-  if (!vals.empty()) {
-    HIP_CHECK(hipMemcpyAsync(vals.data(), L.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
-    HIP_CHECK(hipMemcpyAsync(tp.data(), L.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-  }
-  HIP_CHECK(hipMemcpyAsync(stat.data(), L.stat, stat.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-  HIP_CHECK(hipStreamSynchronize(m.stream));
-  // (the probe ring's clock: probe_history)
-  return wall_heat_history_from(wallq_plan, wallq_opts, vals.data(), tp.data(), (long)ws.s.samples, stat.data(), ws.s,
-                                [&](double t) {
-                                  const real part = t - time_offset;
-                                  return (double)(cs.global_time + part);
-                                });
+  return wall_heat_history_from(wallq_plan, wallq_opts, impl->ring_read(impl->wallq.ring, (size_t)wallq_plan.nentries()),
+                                [&](double t) { return host_time(t); });
 }
 
-// After the other observers' launches; the same view, and for the lean N-S /
-// mechanism state the materialise fill's (as launch_loads).  Nothing here
-// allocates, copies or synchronises.
-void DeviceSolver::launch_wall_heat(const StepParams& P, int slot, int slot_next) {
+void DeviceSolver::launch_wall_heat(const StepParams& P, const PostStep& v) {
   Impl& m = *impl;
-  SoA s;
-  const int kind = post_step_view(s);
-  SoA fin = s, out = s;
-  // the dt slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3, else (nstep + 2) % 3)
-  int fslot = slot;
-  if (lns_state) {
-    lns_fill_views(fin, out);
-    if (kind == PR_SGL) fslot = slot_next;
-  }
   const WallHeatDev& L = m.wallq;
-  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.sc, m.sc, L.cap);
+  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.ring.sc, m.sc, L.ring.cap);
   HIP_CHECK(hipGetLastError());
   if (L.ncells > 0) {
     const dim3 g((unsigned)((L.ncells + WALLQ_BLOCK - 1) / WALLQ_BLOCK)), b(WALLQ_BLOCK);
-    switch (kind) {
-      case PR_SGL: hipLaunchKernelGGL(hf2d_wallq_cells<PR_SGL>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_SGT: hipLaunchKernelGGL(hf2d_wallq_cells<PR_SGT>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_MECH: hipLaunchKernelGGL(hf2d_wallq_cells<PR_MECH>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_LEAN: hipLaunchKernelGGL(hf2d_wallq_cells<PR_LEAN>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      default: hipLaunchKernelGGL(hf2d_wallq_cells<PR_GATHER>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-    }
+    with_kind(v.kind, [&](auto K) {
+      hipLaunchKernelGGL(hf2d_wallq_cells<decltype(K)::value>, g, b, 0, m.stream, P, v.s, v.fin, v.out, L, m.sc, v.fslot);
+    });
     HIP_CHECK(hipGetLastError());
   }
   hipLaunchKernelGGL(hf2d_wallq_fold, dim3((unsigned)(L.nx + L.ny)), dim3(WALLQ_BLOCK), 0, m.stream, L, m.sc);
@@ -586,120 +489,53 @@ void DeviceSolver::record_surface(const SurfaceOpts& o) {
   // (a refused plan throws here and leaves the armed recorder, if any, whole:
   // its options, plan, ring and statistics are replaced only together, below)
   SurfacePlan P = surf_plan_build(o);
-  const int cap = (int)std::min<long>(o.capacity, 0x7fffffffL);
-  surf_ring_alloc(P, cap);
-  SurfaceDev& L = m.surf;
-  if (!L.sc) L.sc = m.mem.alloc<WallHeatScalars>(1);
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
+  HIP_CHECK(hipDeviceSynchronize());   // (the steps flush_pending launched: nothing in flight reads the arrays)
   surf_armed = false;
+  SampleRing& r = m.surf.ring;
+  m.ring_alloc(m.surf_mem.ring, r, P.nentries(), (int)std::min<long>(o.capacity, 0x7fffffffL));
+  r.statistics = o.statistics ? 1 : 0;
   surf_plan_upload(std::move(P));
   surf_opts = o;
-  surf_opts.capacity = cap;
-  L.cap = cap;
-  L.statistics = o.statistics ? 1 : 0;
-  surf_reset();
+  surf_opts.capacity = r.cap;
+  m.ring_reset(r, surf_plan.nentries(), o.every, o.step_weight, time_offset);
   surf_armed = true;
 }
 
 // The plan of the options over the records the backend holds now.  Throws
-// where a value could not be recorded exactly: the wall heat recorder's
-// refusals (wallq_plan_build), for the same reasons.
+// where a value could not be recorded exactly.
 SurfacePlan DeviceSolver::surf_plan_build(const SurfaceOpts& o) const {
   SurfacePlan P = build_surface_plan(cs, cs.J, o, l_off);
   for (long c : P.cells)
     if (c < 0 || c >= h.N) throw std::runtime_error("surface recorder: a needed cell lies outside the solver's arrays");
-  if (P.nnodes() > 0 && (lns_ok || lnm_ok) && cs.cfg.ProblemType == SM_NS && !cs.cfg.isTurbulenceReset &&
-      cs.cfg.TurbStartIter >= 2 && last_iter + iter < (long)cs.cfg.TurbStartIter)
-    throw std::runtime_error("surface recorder: wall nodes on the lean N-S / mechanism state cannot be recorded "
-                             "exactly before TurbStartIter has passed; arm (or upload) later");
-  if (P.nnodes() > 0 && lean_ok && !lean_sg_ok && make_params(last_iter + iter).chem_model != NO_REACTIONS)
-    throw std::runtime_error("surface recorder: a reacting gas mixture on the lean inviscid step stores no wall "
-                             "temperature between outputs; the recorder cannot be armed on this deck");
+  if (P.nnodes() > 0) refuse_wall_nodes("surface recorder", "wall nodes", true);
   return P;
-}
-
-// Ring and statistics arrays for the plan's node count and `cap` rows (used
-// again where they are large enough).
-void DeviceSolver::surf_ring_alloc(const SurfacePlan& P, int cap) {
-  Impl& m = *impl;
-  const size_t ne = (size_t)SURFACE_NVARS * P.nnodes(), nv = (size_t)cap * ne;
-  if (nv > m.surf_vals_cap) {
-    m.surf_vals = m.mem.alloc<real>(nv);
-    m.surf_vals_cap = nv;
-  }
-  if ((size_t)cap > m.surf_times_cap) {
-    m.surf_times = m.mem.alloc<double>((size_t)cap);
-    m.surf_times_cap = (size_t)cap;
-  }
-  if (4 * ne > m.surf_stat_cap) {
-    m.surf_stat = m.mem.alloc<double>(4 * ne);
-    m.surf_stat_cap = 4 * ne;
-  }
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets)
-  m.surf.vals = m.surf_vals;
-  m.surf.times = m.surf_times;
-  m.surf.stat = m.surf_stat;
 }
 
 // A built plan into the device arrays (used again where they are large
 // enough; the stream is idle: flush_pending / upload synchronised it).
 void DeviceSolver::surf_plan_upload(SurfacePlan&& P) {
   Impl& m = *impl;
-  const long nc = P.ncells(), nn = P.nnodes();
-  if (nc > m.surf_cells_cap) {
-    m.surf_cells = m.mem.alloc<long>((size_t)nc);
-    m.surf_mask = m.mem.alloc<uint8_t>((size_t)nc);
-    m.surf_scratch = m.mem.alloc<real>((size_t)SURFACE_PLANES * nc);
-    m.surf_cells_cap = nc;
-  }
-  if (nn > m.surf_nodes_cap) {
-    m.surf_idx = m.mem.alloc<int>((size_t)SURFACE_IDX * nn);
-    m.surf_bits = m.mem.alloc<uint8_t>((size_t)nn);
-    m.surf_nodes_cap = nn;
-  }
-  HIP_CHECK(hipDeviceSynchronize());   // (the allocator's memsets, and nothing in flight reads the arrays)
-  auto cp = [&](void* d, const void* s, size_t bytes) {
-    if (bytes) HIP_CHECK(hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, m.stream));
-  };
-  cp(m.surf_cells, P.cells.data(), nc * sizeof(long));
-  cp(m.surf_mask, P.mask.data(), nc * sizeof(uint8_t));
-  cp(m.surf_idx, P.idx.data(), (size_t)SURFACE_IDX * nn * sizeof(int));
-  cp(m.surf_bits, P.bits.data(), nn * sizeof(uint8_t));
-  HIP_CHECK(hipStreamSynchronize(m.stream));
+  auto& a = m.surf_mem;
   SurfaceDev& L = m.surf;
   L.K = P.K;
-  L.cells = m.surf_cells;
-  L.mask = m.surf_mask;
-  L.idx = m.surf_idx;
-  L.bits = m.surf_bits;
-  L.scratch = m.surf_scratch;
-  L.ncells = nc;
-  L.nnodes = nn;
+  L.ncells = P.ncells();
+  L.nnodes = P.nnodes();
+  L.scratch = m.grown(a.scratch, (size_t)SURFACE_PLANES * L.ncells);
+  L.cells = m.plan_array(a.cells, P.cells);
+  L.mask = m.plan_array(a.mask, P.mask);
+  L.idx = m.plan_array(a.idx, P.idx);
+  L.bits = m.plan_array(a.bits, P.bits);
+  HIP_CHECK(hipStreamSynchronize(m.stream));
   surf_plan = std::move(P);
   surf_friction = surf_plan.friction();
-  surf_gen++;   // windows captured so far must not replay (mode_signature)
-}
-
-// An empty ring and empty statistics whose clock starts at the present value.
-void DeviceSolver::surf_reset() {
-  Impl& m = *impl;
-  WallHeatScalars s0{};
-  s0.s.every = surf_opts.every;
-  s0.s.step_weight = surf_opts.step_weight ? 1 : 0;
-  s0.s.t_off = time_offset;
-  HIP_CHECK(hipMemcpyAsync(m.surf.sc, &s0, sizeof s0, hipMemcpyHostToDevice, m.stream));
-  const size_t ne = (size_t)SURFACE_NVARS * surf_plan.nnodes();
-  if (ne) HIP_CHECK(hipMemsetAsync(m.surf.stat, 0, 4 * ne * sizeof(double), m.stream));
-  hipLaunchKernelGGL(hf2d_stats_rebase, dim3(1), dim3(64), 0, m.stream, &m.surf.sc->s, m.sc);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(m.stream));
+  observers_gen++;
 }
 
 void DeviceSolver::clear_surface() {
   if (!surf_armed) return;
   flush_pending();
   HIP_CHECK(hipSetDevice(dev));
-  surf_reset();
+  impl->ring_reset(impl->surf.ring, surf_plan.nentries(), surf_opts.every, surf_opts.step_weight, time_offset);
 }
 
 const SurfacePlan& DeviceSolver::surface_plan() const {
@@ -711,60 +547,42 @@ SurfaceHistory DeviceSolver::surface_history() {
   if (!surf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
   flush_pending();
   HIP_CHECK(hipSetDevice(dev));
-  Impl& m = *impl;
-  const SurfaceDev& L = m.surf;
-  const size_t ne = (size_t)SURFACE_NVARS * surf_plan.nnodes();
-  WallHeatScalars ws;
-  std::vector<real> vals((size_t)L.cap * ne);
-  std::vector<double> tp((size_t)L.cap), stat(4 * ne);
-  HIP_CHECK(hipMemcpyAsync(&ws, L.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
-  if (!vals.empty())
-    HIP_CHECK(hipMemcpyAsync(vals.data(), L.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
-  if (!tp.empty())
-    HIP_CHECK(hipMemcpyAsync(tp.data(), L.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-  if (!stat.empty())
-    HIP_CHECK(hipMemcpyAsync(stat.data(), L.stat, stat.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
-  HIP_CHECK(hipStreamSynchronize(m.stream));
-  // (the probe ring's clock: probe_history)
-  return surface_history_from(surf_plan, surf_opts, vals.data(), tp.data(), (long)ws.s.samples, stat.data(), ws.s,
-                              [&](double t) {
-                                const real part = t - time_offset;
-                                return (double)(cs.global_time + part);
-                              });
+  return surface_history_from(surf_plan, surf_opts, impl->ring_read(impl->surf.ring, surf_plan.nentries()),
+                              [&](double t) { return host_time(t); });
 }
 
-// After the other observers' launches; the same view, and for the lean N-S /
-// mechanism state the materialise fill's (as launch_loads).  Nothing here
-// allocates, copies or synchronises.
-void DeviceSolver::launch_surface(const StepParams& P, int slot, int slot_next) {
+void DeviceSolver::launch_surface(const StepParams& P, const PostStep& v) {
   Impl& m = *impl;
-  SoA s;
-  const int kind = post_step_view(s);
-  SoA fin = s, out = s;
-  // the dt slot of lns_materialize's fill, which runs after nstep++ (SGL: nstep % 3, else (nstep + 2) % 3)
-  int fslot = slot;
-  if (lns_state) {
-    lns_fill_views(fin, out);
-    if (kind == PR_SGL) fslot = slot_next;
-  }
   const SurfaceDev& L = m.surf;
-  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.sc, m.sc, L.cap);
+  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.ring.sc, m.sc, L.ring.cap);
   HIP_CHECK(hipGetLastError());
   if (L.ncells > 0) {
     const dim3 g((unsigned)((L.ncells + SURF_BLOCK - 1) / SURF_BLOCK)), b(SURF_BLOCK);
-    switch (kind) {
-      case PR_SGL: hipLaunchKernelGGL(hf2d_surf_cells<PR_SGL>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_SGT: hipLaunchKernelGGL(hf2d_surf_cells<PR_SGT>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_MECH: hipLaunchKernelGGL(hf2d_surf_cells<PR_MECH>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      case PR_LEAN: hipLaunchKernelGGL(hf2d_surf_cells<PR_LEAN>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-      default: hipLaunchKernelGGL(hf2d_surf_cells<PR_GATHER>, g, b, 0, m.stream, P, s, fin, out, L, m.sc, fslot); break;
-    }
+    with_kind(v.kind, [&](auto K) {
+      hipLaunchKernelGGL(hf2d_surf_cells<decltype(K)::value>, g, b, 0, m.stream, P, v.s, v.fin, v.out, L, m.sc, v.fslot);
+    });
     HIP_CHECK(hipGetLastError());
   }
   // (at least one workgroup: the sample's time is written for a plan without nodes too)
   const long gn = L.nnodes > 0 ? (L.nnodes + SURF_BLOCK - 1) / SURF_BLOCK : 1;
   hipLaunchKernelGGL(hf2d_surf_nodes, dim3((unsigned)gn), dim3(SURF_BLOCK), 0, m.stream, L, m.sc);
   HIP_CHECK(hipGetLastError());
+}
+
+// upload() replaced the records under the armed recorders: the same targets
+// and options over the new flags.  The load ring keeps its shape (as many
+// lists as before) and so does the wall heat ring (nx, ny never change);
+// another node count restarts the surface recorder's ring and statistics.
+void DeviceSolver::plans_rebuild() {
+  Impl& m = *impl;
+  if (loads_cap) loads_plan_upload(loads_plan_build(loads_boxes, loads_cuts));
+  if (wallq_armed) wallq_plan_upload(wallq_plan_build(wallq_opts));
+  if (!surf_armed) return;
+  const size_t ne = surf_plan.nentries();
+  surf_plan_upload(surf_plan_build(surf_opts));
+  if (surf_plan.nentries() == ne) return;
+  m.ring_alloc(m.surf_mem.ring, m.surf.ring, surf_plan.nentries(), m.surf.ring.cap);
+  m.ring_reset(m.surf.ring, surf_plan.nentries(), surf_opts.every, surf_opts.step_weight, time_offset);
 }
 
 // ---------------------------------------------------------------------------
@@ -809,7 +627,7 @@ void DeviceSolver::start_averaging(int every, bool second_moments, bool step_wei
   stats_favre = favre;
   stats_species = species;
   stats_on = stats_armed = true;
-  stats_gen++;   // windows captured so far must not replay (mode_signature)
+  observers_gen++;
 }
 
 void DeviceSolver::reset_averaging() {
@@ -826,7 +644,7 @@ void DeviceSolver::stop_averaging() {
   if (!stats_on) return;
   flush_pending();
   stats_on = false;
-  stats_gen++;   // the cached windows hold the accumulate nodes
+  observers_gen++;   // the cached windows hold the accumulate nodes
 }
 
 FlowAverages DeviceSolver::averages() {
@@ -902,10 +720,9 @@ static void launch_stats_x_kind(hipStream_t st, unsigned nblk, bool second, bool
     hipLaunchKernelGGL((hf2d_stats_accum_x<KIND, false, false>), g, b, 0, st, P, s, f, x);
 }
 
-void DeviceSolver::launch_stats(const StepParams& P) {
+void DeviceSolver::launch_stats(const StepParams& P, const PostStep& v) {
   Impl& m = *impl;
-  SoA s;
-  const int kind = post_step_view(s);
+  const SoA& s = v.s;
   const FlowStats& f = m.stats;
   hipLaunchKernelGGL(hf2d_stats_tick, dim3(1), dim3(64), 0, m.stream, f.sc, m.sc);
   HIP_CHECK(hipGetLastError());
@@ -914,22 +731,11 @@ void DeviceSolver::launch_stats(const StepParams& P) {
     const StatsExt& x = m.stats_x;
     // (a listed species is a plane of the view's block: check_averaging)
     if (x.ns > 0 && (!s.Ys || s.nsp != h.nsp)) throw std::runtime_error("flow statistics: the step's view holds no species block");
-    switch (kind) {
-      case PR_SGL: launch_stats_x_kind<PR_SGL>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
-      case PR_SGT: launch_stats_x_kind<PR_SGT>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
-      case PR_MECH: launch_stats_x_kind<PR_MECH>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
-      case PR_LEAN: launch_stats_x_kind<PR_LEAN>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
-      default: launch_stats_x_kind<PR_GATHER>(m.stream, nblk, stats_second, stats_favre, P, s, f, x); break;
-    }
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  switch (kind) {
-    case PR_SGL: launch_stats_kind<PR_SGL>(m.stream, nblk, stats_second, P, s, f); break;
-    case PR_SGT: launch_stats_kind<PR_SGT>(m.stream, nblk, stats_second, P, s, f); break;
-    case PR_MECH: launch_stats_kind<PR_MECH>(m.stream, nblk, stats_second, P, s, f); break;
-    case PR_LEAN: launch_stats_kind<PR_LEAN>(m.stream, nblk, stats_second, P, s, f); break;
-    default: launch_stats_kind<PR_GATHER>(m.stream, nblk, stats_second, P, s, f); break;
+    with_kind(v.kind, [&](auto K) {
+      launch_stats_x_kind<decltype(K)::value>(m.stream, nblk, stats_second, stats_favre, P, s, f, x);
+    });
+  } else {
+    with_kind(v.kind, [&](auto K) { launch_stats_kind<decltype(K)::value>(m.stream, nblk, stats_second, P, s, f); });
   }
   HIP_CHECK(hipGetLastError());
 }

@@ -1,8 +1,11 @@
 // Plain argument blocks and constants of the lean N-S step (lean_ns.hpp), the
-// lean mechanism step (lean_mech.hpp) and the probe recorder (probe_history.hpp):
+// lean mechanism step (lean_mech.hpp) and the per-step observers (probe, load,
+// wall heat and surface recorders; their post-step view and kind dispatch):
 // what DeviceSolver::Impl and the host code of every unit need of them, without
 // the families' device code.
 #pragma once
+
+#include <type_traits>
 
 #include "../core/lean_euler.hpp"
 #include "../core/wall_heat.hpp"
@@ -89,6 +92,32 @@ constexpr int PROBE_MAX = 64;    // one lane per probe
 constexpr int PROBE_VARS = 5;    // p, T, rho, U, V
 enum { PR_GATHER = 0, PR_SGL = 1, PR_SGT = 2, PR_MECH = 3, PR_LEAN = 4 };
 
+// What every observer's launches read after a step (DeviceSolver::post_step):
+// the PR_* kind and the view of the representation that is authoritative now;
+// for the lean N-S / mechanism state the views of the fill lns_materialize
+// would run (else the same view) and the dt slot that fill reads.
+struct PostStep {
+  int kind = PR_GATHER;
+  SoA s, fin, out;
+  int fslot = 0;
+};
+
+// The run-time kind as a compile-time constant: f(std::integral_constant<int, PR_*>).
+// The one switch over the kinds.  LEAN false: PR_LEAN runs as PR_GATHER and f
+// is not instantiated for it (the load recorder has no kernel of that kind).
+template <bool LEAN = true, class F>
+inline void with_kind(int kind, F&& f) {
+  switch (kind) {
+    case PR_SGL: return f(std::integral_constant<int, PR_SGL>{});
+    case PR_SGT: return f(std::integral_constant<int, PR_SGT>{});
+    case PR_MECH: return f(std::integral_constant<int, PR_MECH>{});
+    case PR_LEAN:
+      if constexpr (LEAN) return f(std::integral_constant<int, PR_LEAN>{});
+      [[fallthrough]];
+    default: return f(std::integral_constant<int, PR_GATHER>{});
+  }
+}
+
 struct ProbeRing {
   const long* idx = nullptr;   // local cell of each probe (< 0: another strip's column)
   int n = 0, cap = 0;
@@ -119,6 +148,16 @@ struct WallHeatScalars {
   StatsScalars s;   // the sampling decision and the weights (stats_tick)
   long slot = 0;    // ring row of this sample
 };
+// The ring of sampled rows and the running statistics of a recorder that ticks
+// on scalars of its own: `ne` entries a row (wall heat: 4 nx + ny; surface:
+// [SURFACE_NVARS][nnodes])
+struct SampleRing {
+  real* vals = nullptr;          // [cap][ne]
+  double* times = nullptr;       // [cap] DevScalars::time_part after the step
+  double* stat = nullptr;        // [4][ne] m, M, peak, peak_time (DevScalars::time_part)
+  WallHeatScalars* sc = nullptr;
+  int cap = 0, statistics = 0;
+};
 struct WallHeatDev {
   WallHeatConst K;
   // the plan (WallHeatPlan)
@@ -127,12 +166,9 @@ struct WallHeatDev {
   const int* off = nullptr;      // [nx + ny + 1]
   const int* list = nullptr;
   long ncells = 0;
-  int nx = 0, ny = 0, cap = 0, statistics = 0;
+  int nx = 0, ny = 0;
   real* scratch = nullptr;       // [3][ncells] lam + lam_t, Tg, p of the needed cells after the step
-  real* vals = nullptr;          // [cap][4 nx + ny]
-  double* times = nullptr;       // [cap] DevScalars::time_part after the step
-  double* stat = nullptr;        // [4][4 nx + ny] m, M, peak, peak_time (DevScalars::time_part)
-  WallHeatScalars* sc = nullptr;
+  SampleRing ring;
 };
 
 // Per-step surface recorder (surface_history.hpp): the plan, the ring and the
@@ -145,12 +181,8 @@ struct SurfaceDev {
   const int* idx = nullptr;        // [nnodes][SURFACE_IDX]
   const uint8_t* bits = nullptr;   // [nnodes] SurfaceNodeBit
   long ncells = 0, nnodes = 0;
-  int cap = 0, statistics = 0;
   real* scratch = nullptr;         // [SURFACE_PLANES][ncells] the needed cells' values after the step
-  real* vals = nullptr;            // [cap][SURFACE_NVARS][nnodes]
-  double* times = nullptr;         // [cap] DevScalars::time_part after the step
-  double* stat = nullptr;          // [4][SURFACE_NVARS][nnodes] m, M, peak, peak_time (DevScalars::time_part)
-  WallHeatScalars* sc = nullptr;
+  SampleRing ring;
 };
 
 }  // namespace hf2d

@@ -83,7 +83,7 @@ HF_HD inline void surf_cell(const StepParams& P, const SoA& s, const SoA& fin, c
 template <int KIND>
 __global__ __launch_bounds__(SURF_BLOCK) void hf2d_surf_cells(StepParams P, SoA s, SoA fin, SoA out, SurfaceDev L,
                                                                const DevScalars* sc, int slot) {
-  if (!L.sc->s.sample) return;
+  if (!L.ring.sc->s.sample) return;
   if (KIND != PR_GATHER && KIND != PR_LEAN) apply_dt(P, sc, slot);
   const long t = (long)blockIdx.x * SURF_BLOCK + threadIdx.x;
   if (t >= L.ncells) return;
@@ -99,24 +99,24 @@ __global__ __launch_bounds__(SURF_BLOCK) void hf2d_surf_cells(StepParams P, SoA 
 // The grid has at least one workgroup, also for a plan without nodes: the
 // sample's time is recorded all the same.
 __global__ __launch_bounds__(SURF_BLOCK) void hf2d_surf_nodes(SurfaceDev L, const DevScalars* sc) {
-  const WallHeatScalars* w = L.sc;
+  const WallHeatScalars* w = L.ring.sc;
   if (!w->s.sample) return;
   const long n = (long)blockIdx.x * SURF_BLOCK + threadIdx.x;
   const long slot = w->slot;
   const double t = sc->time_part;
-  if (n == 0 && L.cap > 0) L.times[slot] = t;
+  if (n == 0 && L.ring.cap > 0) L.ring.times[slot] = t;
   if (n >= L.nnodes) return;
   real out[SURFACE_NVARS];
   surface_node(L.K, L.idx, L.bits, L.scratch, L.ncells, n, out);
   const long ne = (long)SURFACE_NVARS * L.nnodes;
   const double wt = w->s.w, r = w->s.r;
   const bool first = w->s.samples == 1;
-  double *m = L.stat, *M = m + ne, *pk = M + ne, *pt = pk + ne;
+  double *m = L.ring.stat, *M = m + ne, *pk = M + ne, *pt = pk + ne;
 #pragma unroll
   for (int v = 0; v < SURFACE_NVARS; v++) {
     const long e = (long)v * L.nnodes + n;
-    if (L.cap > 0) L.vals[slot * ne + e] = out[v];
-    if (L.statistics) wall_heat_stat(wt, r, t, first, (double)out[v], m[e], M[e], pk[e], pt[e]);
+    if (L.ring.cap > 0) L.ring.vals[slot * ne + e] = out[v];
+    if (L.ring.statistics) wall_heat_stat(wt, r, t, first, (double)out[v], m[e], M[e], pk[e], pt[e]);
   }
 }
 #endif

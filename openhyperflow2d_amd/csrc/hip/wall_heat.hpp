@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64) void hf2d_wallq_tick(WallHeatScalars* w, const 
 template <int KIND>
 __global__ __launch_bounds__(WALLQ_BLOCK) void hf2d_wallq_cells(StepParams P, SoA s, SoA fin, SoA out, WallHeatDev L,
                                                                  const DevScalars* sc, int slot) {
-  if (!L.sc->s.sample) return;
+  if (!L.ring.sc->s.sample) return;
   if (KIND != PR_GATHER && KIND != PR_LEAN) apply_dt(P, sc, slot);
   const long t = (long)blockIdx.x * WALLQ_BLOCK + threadIdx.x;
   if (t >= L.ncells) return;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(WALLQ_BLOCK) void hf2d_wallq_cells(StepParams P, So
 __global__ __launch_bounds__(WALLQ_BLOCK) void hf2d_wallq_fold(WallHeatDev L, const DevScalars* sc) {
   __shared__ real tq[WALLQ_BLOCK], ta[WALLQ_BLOCK];
   __shared__ real last[2];   // Cp, St of the list's last node
-  const WallHeatScalars* w = L.sc;
+  const WallHeatScalars* w = L.ring.sc;
   if (!w->s.sample) return;
   const int l = (int)blockIdx.x, tid = (int)threadIdx.x;   // (the grid has nx + ny workgroups)
   const int b = L.off[l], e = L.off[l + 1];
@@ -150,15 +150,15 @@ __global__ __launch_bounds__(WALLQ_BLOCK) void hf2d_wallq_fold(WallHeatDev L, co
   const long ne = (long)WALL_HEAT_X * L.nx + L.ny, slot = w->slot;
   const double t = sc->time_part, wt = w->s.w, r = w->s.r;
   const bool first = w->s.samples == 1;
-  double *m = L.stat, *M = m + ne, *pk = M + ne, *pt = pk + ne;
+  double *m = L.ring.stat, *M = m + ne, *pk = M + ne, *pt = pk + ne;
 #pragma unroll
   for (int k = 0; k < WALL_HEAT_X; k++) {
     if (k > 0 && !col) break;
     const int en = wall_heat_entry(L.nx, l, k);
-    if (L.cap > 0) L.vals[slot * ne + en] = out[k];
-    if (L.statistics) wall_heat_stat(wt, r, t, first, (double)out[k], m[en], M[en], pk[en], pt[en]);
+    if (L.ring.cap > 0) L.ring.vals[slot * ne + en] = out[k];
+    if (L.ring.statistics) wall_heat_stat(wt, r, t, first, (double)out[k], m[en], M[en], pk[en], pt[en]);
   }
-  if (l == 0 && L.cap > 0) L.times[slot] = t;
+  if (l == 0 && L.ring.cap > 0) L.ring.times[slot] = t;
 }
 #endif
 

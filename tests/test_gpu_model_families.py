@@ -134,6 +134,83 @@ def test_recorder_and_averages_across_a_cycle_match_cpu(gpu, tmp_path):
         np.testing.assert_array_equal(ag[k], ac[k], err_msg=k)
 
 
+def test_load_heat_and_surface_recorders_across_a_cycle_match_cpu(gpu, tmp_path):
+    """The same roll for the three recorders that carry a plan: the load ring's
+    times, the wall heat and surface rings' times, their peak times and the
+    offsets of their weights' clocks all move by the device's time_part at the
+    boundary.  All five observers armed before run() on the k-eps deck with wall
+    heat transfer (split SK_SGT kernels), cycle boundary after step 30 of 43.
+
+    On the GPU alone, bit for bit: one clock (every history's times are the
+    probe history's, strictly increasing, ending at summary()["time"]), every
+    peak time is one of those times, and the three weight sums are one number.
+    A block of the roll that shifts by another amount or misses an array breaks
+    one of the three.  Against the CPU recorders: the row's rule, REL of the
+    CPU array's largest magnitude."""
+    import numpy as np
+
+    from tests.test_gpu_load_history import targets
+
+    row = mf.BY_ID["monitors_heatflux_cx"]
+    g, c = mf.simulation(gpu, row, "gpu"), mf.simulation(gpu, row, "cpu", lean=False)
+    _viscous_facts(g.solver)
+    cells = [(3, 2), (60, 20), (117, 37)]
+    out = []
+    for s in (g, c):
+        assert all(s.field("solid")[i, j] == 0.0 for i, j in cells)
+        s.record_probes(cells, capacity=64)
+        s.start_averaging()
+        s.record_loads(*targets(s.case), capacity=64)
+        s.record_wall_heat(capacity=64)
+        s.record_surface(capacity=64)
+        assert list(mf.march(s, tmp_path)) == [0, 1, 2, 3]
+        out.append((s.probe_history(), s.averages(), s.load_history(), s.wall_heat_history(), s.surface_history(),
+                    s.summary()))
+    (pg, ag, lg, wg, fg, sg), (pc, ac, lc, wc, fc, sc) = out
+    assert sg["iteration"] == sc["iteration"] == 43
+    for h in (pg, lg, wg, fg, pc, lc, wc, fc):
+        assert h["total"] == 43
+    for h in (ag, wg, fg, ac, wc, fc):
+        assert h["samples"] == 43
+
+    # the CPU twin: what the deck gives the recorders, and none of it constant
+    assert (int(wc["x_nodes"].sum()), int(wc["y_nodes"].sum()), len(fc["i"])) == (80, 83, 84)
+    assert ((fc["fric_x"] != 0) | (fc["fric_y"] != 0)).all()   # (every surface node has a friction term)
+    twin = {"forces": lc["forces"], "mass_flow": lc["mass_flow"], "x": wc["x"], "y": wc["y"], "values": fc["values"]}
+    for k, a in twin.items():
+        assert np.isfinite(a).all() and a.shape[0] == 43, k
+        assert (a.reshape(43, -1).max(axis=0) > a.reshape(43, -1).min(axis=0)).any(), k + " is constant"
+    t_roll = pc["times"][29]
+    assert (fc["peak_time"] <= t_roll).any() and (fc["peak_time"] > t_roll).any()
+
+    # one clock on the device
+    times = pg["times"]
+    for name, h in (("loads", lg), ("wall heat", wg), ("surface", fg)):
+        np.testing.assert_array_equal(h["times"], times, err_msg=name)
+    assert (np.diff(times) > 0).all() and times[-1] == sg["time"]
+    for name, pt in (("surface", fg["peak_time"]), ("wall heat x", wg["peak_time_x"]), ("wall heat y", wg["peak_time_y"])):
+        stray = ~np.isin(pt, times)
+        assert not stray.any(), "%s: %d peak times are no sample's time, e.g. %r" % (name, stray.sum(), pt[stray][:3])
+    assert (fg["peak_time"] <= times[29]).any() and (fg["peak_time"] > times[29]).any()
+    assert wg["time"] == fg["time"] == ag["time"], (wg["time"], fg["time"], ag["time"])
+
+    # against the CPU recorders
+    pairs = [("forces", lg["forces"], lc["forces"]), ("mass_flow", lg["mass_flow"], lc["mass_flow"]),
+             ("loads times", lg["times"], lc["times"])]
+    pairs += [("wall heat " + k, wg[k], wc[k]) for k in ("x", "y", "mean_x", "mean_y", "peak_x", "peak_y", "times", "time")]
+    pairs += [("surface " + k, fg[k], fc[k]) for k in ("values", "mean", "peak", "times", "time")]
+    pairs += [("probe times", pg["times"], pc["times"]), ("averages time", ag["time"], ac["time"])]
+    bad = []
+    for name, x, y in pairs:
+        x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+        assert x.shape == y.shape, name
+        top, d = float(np.abs(y).max()), float(np.abs(x - y).max())
+        print("%s: max |gpu - cpu| %.3e, max |cpu| %.6e" % (name, d, top))
+        if not d <= mf.REL * top:   # (a NaN misses)
+            bad.append("%s: max |diff| %.3e > %.1e * %.6e" % (name, d, mf.REL, top))
+    assert not bad, "\n".join(bad)
+
+
 @pytest.mark.parametrize("rid", [r.id for r in mf.LNS])
 def test_lean_ns_tiles_across_a_cycle_match_cpu(gpu, tmp_path, rid):
     """hf2d_lns_step<SK_SGT, k-eps | Spalart-Allmaras> through the cycle
