@@ -113,10 +113,17 @@ __device__ double T_from_e(const double* c, double rho, double e, double T0) {
 // Species that appear in no reaction (an inert bath gas such as N2: only a
 // collision partner) have a zero production rate, so their row of I - h J is
 // the identity row and their solution component is 0 / 1 = +0; their column
-// (third-body efficiencies) then only ever multiplies that zero, and the
-// elimination never pivots on their row (its other entries are zero).  The
-// system is therefore solved over the reacting species alone -- bit for bit
-// the same increments, and 9 x 10 -> 8 x 9 doubles of registers for H2 / air.
+// (third-body efficiencies) then only ever multiplies that zero.  The system
+// is therefore solved over the reacting species alone: 9 x 10 -> 8 x 9
+// doubles of registers for H2 / air.  Against the full system this gives bit
+// for bit the same increments where the inert species are listed last (H2 /
+// air): the full elimination reaches their columns with no other row left to
+// pivot on, and pivoting on an identity row with a zero right-hand side
+// changes nothing.  For an inert species listed earlier the full elimination
+// may prefer a row with |h J| > 1 in that column to the identity row, so
+// there the two agree to rounding only (tests/test_gpu_kinetics_edges.py
+// holds a permuted mechanism to the bound against the host integrator, which
+// solves the full system).
 template <class M>
 struct Reacting {
   struct Map {

@@ -8,63 +8,14 @@ import pytest
 
 from openhyperflow2d_amd.ops import chemistry as ch
 from openhyperflow2d_amd.ops import mechanism as M
-
-
-def _random_mech(ns, nr, seed, reversible=True):
-    """Random mechanism over species of equal molar mass (so a step conserves
-    mass when its coefficient sums agree), reversible / irreversible / third-body
-    steps of orders 1..3."""
-    rng = np.random.default_rng(seed)
-    n2 = M.h2_air_li2004().species[-1]
-    sp = []
-    for i in range(ns):
-        # N2-like thermo with the formation enthalpy / entropy constants shifted by
-        # up to +-2000 K / +-2: moderate equilibrium constants and heat release
-        lo, hi = list(n2.low), list(n2.high)
-        dh, ds = rng.uniform(-2000, 2000), rng.uniform(-2, 2)
-        lo[5] += dh
-        hi[5] += dh
-        lo[6] += ds
-        hi[6] += ds
-        sp.append(M.Species("S%d" % i, 0.02, n2.Tlo, n2.Tmid, n2.Thi, lo, hi, n2.sigma, n2.eps_k))
-    names = [s.name for s in sp]
-    rx = []
-    for r in range(nr):
-        k = int(rng.integers(1, 4))
-        reac = {names[i]: int(rng.integers(1, 3)) for i in rng.choice(ns, size=k, replace=False)}
-        order = sum(reac.values())
-        # equal molar masses: mass balance <=> equal total coefficients
-        pk = int(rng.integers(1, min(3, order) + 1))
-        prods = list(rng.choice(ns, size=pk, replace=False))
-        prod = {names[i]: 0 for i in prods}
-        for t in range(order):
-            prod[names[prods[t % pk]]] += 1
-        if any(v > 3 for v in prod.values()):
-            prod = {names[prods[0]]: min(order, 3)}
-            if order > 3:
-                continue
-            prod[names[prods[0]]] = order
-        tb = bool(rng.random() < 0.2)
-        rx.append(M.Reaction(reac, prod, float(10 ** rng.uniform(-1, 2)), float(rng.uniform(-1, 1)),
-                             float(rng.uniform(0, 3000)), reversible=reversible and bool(rng.random() < 0.7),
-                             third_body=tb, eff={names[0]: 2.0} if tb else {}))
-    return M.Mechanism("rand%d" % seed, sp, rx)
+from tests.kinetics_cases import random_case as _random_case
+from tests.kinetics_cases import random_mech as _random_mech
 
 
 def test_random_mechanism_text_roundtrip():
     m = _random_mech(10, 17, 3)
     m2 = M.Mechanism.from_text(m.to_text())
     assert m2.to_text() == m.to_text()
-
-
-def _random_case(ns, nr):
-    m = _random_mech(ns, nr, ns)
-    rng = np.random.default_rng(ns + nr)
-    n = 16 * 9 + 7
-    Y = rng.random((ns, n)) * 0.05 + 1e-4
-    T = 900.0 + 1500.0 * rng.random(n)
-    rho = Y.sum(0)
-    return m, Y, rho, M.mixture_e(m, (Y / rho).T, T), T
 
 
 @pytest.mark.parametrize("ns,nr", [(3, 5), (10, 17), (13, 21), (16, 40)])
