@@ -298,8 +298,10 @@ StepParams SolverBase::make_params(long it) const {
   P.dx = C.dx;
   P.dy = C.dy;
   P.dt = dt;
-  P.dtdx = dt / C.dx;
-  P.dtdy = dt / C.dy;
+  // (the spacings as the kernels hold them: Config keeps them in double, and in
+  // the FP32 build dt / 0.001 is not dt / 0.001f, which the device forms, apply_dt)
+  P.dtdx = dt / P.dx;
+  P.dtdy = dt / P.dy;
   P.dyy = C.dx / (C.dx + C.dy);
   P.dxx = C.dy / (C.dx + C.dy);
   const real beta_scen = C.beta_Scenario.eval((real)it);
@@ -600,7 +602,7 @@ void SolverBase::write_profile(const std::string& path, int cycles) const {
                  kv.second.first, kv.second.second);
     first = false;
   }
-  std::fprintf(f, "}}\n");
+  std::fprintf(f, "}, \"path\": {%s}}\n", profile_path_facts().c_str());
   std::fclose(f);
 }
 

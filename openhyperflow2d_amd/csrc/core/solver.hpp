@@ -187,6 +187,9 @@ class SolverBase {
   // Full DEEPS2D_Run driver.  Returns the number of cycles run.
   int run(const RunOptions& opt, std::ostream* log);
   void write_profile(const std::string& path, int cycles) const;
+  // the members of the profile's "path" object (JSON, without the braces):
+  // which stepper and kernels the backend ran; empty for a backend with one path
+  virtual std::string profile_path_facts() const { return std::string(); }
 
   // Backend interface
   virtual StepResult do_step(const StepParams& P, bool want_res) = 0;

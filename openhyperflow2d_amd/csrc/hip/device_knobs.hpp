@@ -19,34 +19,34 @@
 #define HF2D_DEVICE_KNOBS(X) \
   /* ---- which stepper runs ---- */ \
   /* Euler: single fused predict+fill kernel */ \
-  X(fused, bool, true, nullptr, true) \
+  X(fused, bool, true, "HF2D_FUSED", true) \
   /* inviscid: lean kernel on the reduced state (lean_euler.hpp) when the case is eligible; takes precedence over `fused` */ \
-  X(lean, bool, true, nullptr, true) \
+  X(lean, bool, true, "HF2D_LEAN", true) \
   /* LDS-tiled lean kernel for all but the first lean step */ \
-  X(lean_tile, bool, true, nullptr, true) \
+  X(lean_tile, bool, true, "HF2D_LEAN_TILE", true) \
   /* single-gas specialisation (lean_euler.hpp) if eligible (lean_sg_ok) */ \
-  X(lean_sg, bool, true, nullptr, true) \
+  X(lean_sg, bool, true, "HF2D_LEAN_SG", true) \
   /* single-gas laminar N-S specialisation (stepkern.hpp fill_cell<SGL>) if eligible (sgl_ok) */ \
-  X(sgl, bool, true, nullptr, true) \
+  X(sgl, bool, true, "HF2D_SGL", true) \
   /* single-gas laminar N-S: one LDS-tiled kernel per step with the fluxes recomputed in the tile (hip/lean_ns.hpp) when eligible (lns_ok) */ \
-  X(lean_ns, bool, true, nullptr, true) \
+  X(lean_ns, bool, true, "HF2D_LEAN_NS", true) \
   /* mechanism mode: the lean step of hip/lean_mech.hpp (tile kernel + kinetics + reacting-cell state kernel) when eligible (lnm_ok) */ \
   X(lean_mech, bool, true, nullptr, true) \
   /* step graphs: 6-step windows captured once and replayed (device_solver.hip) */ \
-  X(use_graph, bool, true, nullptr, false) \
+  X(use_graph, bool, true, "HF2D_GRAPH", false) \
   /* ThreadBlockSize = 0 times the lean tile geometries before the first step; 0: skip the search */ \
   X(autotune_enabled, bool, true, "HF2D_AUTOTUNE", false) \
   /* ---- inviscid lean tile kernel ---- */ \
   /* tile height override (0: auto, ny split in <= 64) */ \
-  X(lean_tj, int, 0, nullptr, true) \
+  X(lean_tj, int, 0, "HF2D_LEAN_TJ", true) \
   /* >0: at most this many tile workgroups resident per CU (LDS request) */ \
   X(lean_wgcu, int, 0, nullptr, true) \
   /* cells per thread in the tiled kernel: 1 or 2 (2: measured ~20% faster) */ \
-  X(lean_cpt, int, 2, nullptr, true) \
+  X(lean_cpt, int, 2, "HF2D_LEAN_CPT", true) \
   /* threads per tile workgroup: 256, or 128 / 64 (single gas; small strips) */ \
-  X(lean_nt, int, 256, nullptr, true) \
+  X(lean_nt, int, 256, "HF2D_LEAN_NT", true) \
   /* compute units (the constructor overwrites it from the device properties): the cpt gate and the stagger rounds */ \
-  X(cu_count, int, 256, nullptr, true) \
+  X(cu_count, int, 256, "HF2D_CU_COUNT", true) \
   /* staggered start of the tile kernel's resident dispatch rounds, 10 ns ticks per round of cu_count workgroups; > 0 whole */ \
   /* rounds, < 0 a linear ramp (headline 2000x200, 1x MI355X, after the fast divide: off 31.3 us, rounds of 1.5 us 29.9 us; */ \
   /* ramp of 0.5 / 1.0 / 1.5 / 2.0 / 3.0 us per round 30.7 / 30.1 / 29.6 / 30.4 / 32.3 us) */ \

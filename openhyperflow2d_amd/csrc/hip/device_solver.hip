@@ -552,6 +552,34 @@ void DeviceSolver::poison_cell(int gi, int j) {
 void DeviceSolver::trace_push(const char* name) { roctxRangePush(name); }
 void DeviceSolver::trace_pop() { roctxRangePop(); }
 
+const char* DeviceSolver::halo_transport() const {
+  const Impl& m = *impl;
+  return m.nranks < 2 ? "none" : m.p2p.on ? "p2p" : m.local ? "local" : m.comm ? "rccl" : "none";
+}
+
+std::string DeviceSolver::profile_path_facts() const {
+  auto quoted = [](const std::string& s) {
+    std::string q = "\"";
+    for (const char ch : s) {
+      if (ch == '"' || ch == '\\') q += '\\';
+      q += (unsigned char)ch < 0x20 ? ' ' : ch;
+    }
+    return q + "\"";
+  };
+  const TileLast& t = lean_tile_last;
+  char b[1024];
+  std::snprintf(b, sizeof b,
+                "\"fp\": %d, \"sk_mode\": %d, \"split_mode\": %d, \"lean_ok\": %s, \"lean_sg_ok\": %s, \"lns_ok\": %s, \"lns_turb\": %d, "
+                "\"lns_steps\": %ld, \"lnm_steps\": %ld, \"graph_captures\": %ld, \"graph_launches\": %ld, "
+                "\"lean_tile_last\": {\"nt\": %d, \"cpt\": %d, \"TI\": %d, \"TJ\": %d, \"nbi\": %d, \"nbj\": %d, "
+                "\"fx\": %d, \"var\": %d, \"seen\": %d}, ",
+                (int)(8 * sizeof(real)), sk_mode, split_mode(), lean_ok ? "true" : "false", lean_sg_ok ? "true" : "false",
+                lns_ok ? "true" : "false", lns_turb, lns_steps, lnm_steps, graph_captures, graph_launches, t.nt, t.cpt,
+                t.TI, t.TJ, t.nbi, t.nbj, t.fx, t.var, t.seen);
+  return std::string(b) + "\"lean_why\": " + quoted(lean_why) + ", \"lns_why\": " + quoted(lns_why) +
+         ", \"transport\": " + quoted(halo_transport());
+}
+
 void DeviceSolver::sync_scalars() {
   flush_pending();
   p2p_complete();

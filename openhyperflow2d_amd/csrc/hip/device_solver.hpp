@@ -140,6 +140,12 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void clear_surface() override;
   void trace_push(const char* name) override;
   void trace_pop() override;
+  // the eligibility results, step counters, last tile launch and halo
+  // transport below, as the Python attributes of the same names give them
+  // (sk_mode: what the case is eligible for; split_mode: what the knobs let
+  // the split stepper run)
+  std::string profile_path_facts() const override;
+  const char* halo_transport() const;   // "none" (one rank), "p2p", "local" or "rccl"
   void synchronize();
   // ThreadBlockSize = 0: time the lean tile geometries, keep the fastest (before the first step)
   std::string autotune(int steps = 120);

@@ -35,6 +35,12 @@ struct LocalHostComm : Comm {
 
 std::shared_ptr<LocalGroup> make_local_group(int n) { return std::make_shared<LocalGroup>(n); }
 
+// RCCL element type of `real` (the halo buffers); the dt words are double /
+// 64-bit patterns in both builds and keep ncclDouble / ncclUint64
+constexpr ncclDataType_t NCCL_REAL = sizeof(real) == 4 ? ncclFloat : ncclDouble;
+static_assert(sizeof(real) == (NCCL_REAL == ncclFloat ? sizeof(float) : sizeof(double)),
+              "NCCL_REAL must have the size of real: the halo counts are in elements of real");
+
 // Host-side reductions of the driver over RCCL (output steps only).
 struct RcclHostComm : Comm {
   ncclComm_t c;
@@ -511,12 +517,12 @@ void DeviceSolver::exchange(int group, int dt_slot, void* on_stream, bool full) 
   } else {
   NCCL_CHECK(ncclGroupStart());
   if (has_left) {
-    NCCL_CHECK(ncclSend(m.halo_send[0], cnt, ncclDouble, m.rank - 1, m.comm, st));
-    NCCL_CHECK(ncclRecv(m.halo_recv[0], cnt, ncclDouble, m.rank - 1, m.comm, st));
+    NCCL_CHECK(ncclSend(m.halo_send[0], cnt, NCCL_REAL, m.rank - 1, m.comm, st));
+    NCCL_CHECK(ncclRecv(m.halo_recv[0], cnt, NCCL_REAL, m.rank - 1, m.comm, st));
   }
   if (has_right) {
-    NCCL_CHECK(ncclSend(m.halo_send[1], cnt, ncclDouble, m.rank + 1, m.comm, st));
-    NCCL_CHECK(ncclRecv(m.halo_recv[1], cnt, ncclDouble, m.rank + 1, m.comm, st));
+    NCCL_CHECK(ncclSend(m.halo_send[1], cnt, NCCL_REAL, m.rank + 1, m.comm, st));
+    NCCL_CHECK(ncclRecv(m.halo_recv[1], cnt, NCCL_REAL, m.rank + 1, m.comm, st));
   }
   if (gather_dt)
     for (int q = 0; q < m.nranks; q++)

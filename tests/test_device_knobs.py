@@ -27,6 +27,10 @@ ENV = {
     "tile_skip_same": "HF2D_SKIP_SAME", "lns_ghost_prologue": "HF2D_GHOST_PROLOGUE", "fx_skip": "HF2D_FX_SKIP",
     "fx_edge_first": "HF2D_FX_EDGE_FIRST", "fx_count1": "HF2D_FX_COUNT1", "lnm_trace": "HF2D_LNM_TRACE",
     "autotune_enabled": "HF2D_AUTOTUNE", "p2p_fuse_wanted": "HF2D_P2P_FUSE",
+    # which stepper runs and the tile geometry: a native CLI (the FP32 build has no other face) reaches them
+    "fused": "HF2D_FUSED", "lean": "HF2D_LEAN", "lean_tile": "HF2D_LEAN_TILE", "lean_sg": "HF2D_LEAN_SG",
+    "sgl": "HF2D_SGL", "lean_ns": "HF2D_LEAN_NS", "use_graph": "HF2D_GRAPH", "lean_tj": "HF2D_LEAN_TJ",
+    "lean_cpt": "HF2D_LEAN_CPT", "lean_nt": "HF2D_LEAN_NT", "cu_count": "HF2D_CU_COUNT",
 }
 
 

@@ -4,7 +4,14 @@ compiled for real = float (_build.gpu_fp32_path; the finite-rate kinetics
 kernels stay FP64-only and the mechanism mode is refused with a message).
 Checked against the FP64 GPU CLI on the same decks: the Tecplot fields agree
 to float rounding away from discontinuities and within a few percent at the
-shocks, and the 680-byte float record is written."""
+shocks, and the 680-byte float record is written.
+
+What this tolerance cannot see, tests/test_gpu_fp32_cells.py does: the float
+GPU against the float CPU stepper, bit for bit on every stepper path.  That
+holds on the 3-gas triple point too (rows three_gas_tile and
+three_gas_two_cell), so the triple point's distance from the FP64 run (one
+run measured 7.2 % against the 5 % asserted below) is float arithmetic that
+the float CPU stepper shares with the kernels, not a kernel defect."""
 import glob
 import os
 import subprocess
