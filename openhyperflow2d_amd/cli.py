@@ -9,6 +9,8 @@
                                      [--load-history FILE.npz [--load-capacity N]]
                                      [--wall-heat FILE.npz [--wall-heat-every K] [--wall-heat-capacity N]]
                                      [--surface FILE.npz [--surface-every K] [--surface-capacity N]]
+                                     [--frames FILE.npz [--frames-vars a,b,...] [--frames-every K]
+                                      [--frames-capacity N] [--frames-stride SI,SJ]]
                                      [--averages FILE.npz [--averages-every K] [--averages-favre]
                                       [--averages-species all|A,B,...]]
   python -m openhyperflow2d_amd deck wedge15 --nx 2000 --ny 200 -o w.dat
@@ -62,6 +64,11 @@ def _cmd_run(a) -> int:
     if a.surface and world > 1:
         if rank == 0:
             print("--surface records in one process only; this is a %d-rank launch "
+                  "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
+        return 2
+    if a.frames and world > 1:
+        if rank == 0:
+            print("--frames records in one process only; this is a %d-rank launch "
                   "(run the deck without torchrun, or drop the option)" % world, file=sys.stderr, flush=True)
         return 2
     if a.averages and world > 1:
@@ -131,6 +138,16 @@ def _cmd_run(a) -> int:
         except (ValueError, RuntimeError) as e:
             print("--surface: %s" % e, file=sys.stderr, flush=True)
             return 2
+    if a.frames:
+        try:
+            stride = tuple(int(v) for v in a.frames_stride.split(","))
+            if len(stride) != 2:
+                raise ValueError("--frames-stride is SI,SJ, not %r" % a.frames_stride)
+            sim.record_frames(vars=[v.strip() for v in a.frames_vars.split(",") if v.strip()], stride=stride,
+                              every=a.frames_every, capacity=a.frames_capacity)
+        except (ValueError, RuntimeError) as e:
+            print("--frames: %s" % e, file=sys.stderr, flush=True)
+            return 2
     if a.averages:
         try:
             sp = a.averages_species
@@ -193,6 +210,14 @@ def _cmd_run(a) -> int:
             np.savez(f, vars=np.asarray(SURFACE_VARS), **{k: np.asarray(v) for k, v in h.items()})
         print("surface: %d of %d samples x 10 x %d nodes -> %s" % (h["times"].shape[0], h["total"],
                                                                    h["values"].shape[2], a.surface), flush=True)
+    if a.frames:
+        import numpy as np
+
+        h = sim.frame_history()
+        with open(a.frames, "wb") as f:   # (np.savez on a path would append ".npz")
+            np.savez(f, **{k: np.asarray(v) for k, v in h.items()})
+        print("frames: %d of %d samples x %d x %d x %d -> %s" % ((h["times"].shape[0], h["total"]) +
+                                                                 h["values"].shape[1:] + (a.frames,)), flush=True)
     if a.averages:
         import numpy as np
 
@@ -324,6 +349,18 @@ def main(argv=None) -> int:
                    help="sample every K-th step (default 1)")
     r.add_argument("--surface-capacity", dest="surface_capacity", type=int, default=4096, metavar="N",
                    help="rows the surface recorder keeps: the last N samples (default 4096; 0: statistics only)")
+    r.add_argument("--frames", metavar="FILE.npz",
+                   help="record whole-field frames of the listed variables after every K-th step (one process only) "
+                        "and write times / values [n, nvars, ni, nj] / total / vars / i / j / x / y / gas to this file")
+    r.add_argument("--frames-vars", dest="frames_vars", default="rho,grad_rho", metavar="a,b,...",
+                   help="variables out of p, T, rho, U, V, grad_rho, grad_p, vorticity, dilatation, ducros "
+                        "(default rho,grad_rho)")
+    r.add_argument("--frames-every", dest="frames_every", type=int, default=1, metavar="K",
+                   help="sample every K-th step (default 1)")
+    r.add_argument("--frames-capacity", dest="frames_capacity", type=int, default=16, metavar="N",
+                   help="frames the recorder keeps: the last N samples (default 16)")
+    r.add_argument("--frames-stride", dest="frames_stride", default="1,1", metavar="SI,SJ",
+                   help="keep every SI-th column and SJ-th row (default 1,1; gradients use the immediate neighbours)")
     r.add_argument("--averages", metavar="FILE.npz",
                    help="accumulate time-averaged p, T, rho, U, V, their variances and the U-V covariance over the "
                         "whole field at every step (one process only) and write mean / var / cov_uv / vars / time / "

@@ -164,6 +164,53 @@ static hf2d::SurfaceOpts surface_opts(py::object boxes, int cp_flow) {
   return o;
 }
 
+// record_frames' / Case.frame's arguments
+static hf2d::FrameOpts frame_opts(const std::vector<std::string>& vars, py::object region, std::pair<int, int> stride,
+                                  int every, long capacity) {
+  hf2d::FrameOpts o;
+  o.vars = vars;
+  o.whole = region.is_none();
+  if (!o.whole) {
+    const auto r = region.cast<std::vector<int>>();
+    if (r.size() != 4) throw py::value_error("frames: a region is (i0, i1, j0, j1)");
+    o.i0 = r[0], o.i1 = r[1], o.j0 = r[2], o.j1 = r[3];
+  }
+  o.si = stride.first;
+  o.sj = stride.second;
+  o.every = every;
+  o.capacity = capacity;
+  return o;
+}
+// The static part of a frame geometry into a dict (Case.frame, frame_history):
+// vars, i, j, x, y (the field dump's coordinates, as the surface table's) and gas
+static void frame_table(py::dict& d, const hf2d::Config& C, const hf2d::FrameGeom& G, const std::vector<uint8_t>& gas) {
+  using namespace hf2d;
+  const real dx_out = (C.dx * C.MaxX) / (C.MaxX - 1);
+  const real dy_out = (C.dy * C.MaxY) / (C.MaxY - 1);
+  py::list names;
+  for (int k = 0; k < G.nvars; k++) names.append(frame_var_names()[G.var[k]]);
+  d["vars"] = py::tuple(names);
+  py::array_t<int> ai(std::vector<py::ssize_t>{(py::ssize_t)G.ni}), aj(std::vector<py::ssize_t>{(py::ssize_t)G.nj});
+  py::array_t<double> ax(std::vector<py::ssize_t>{(py::ssize_t)G.ni}), ay(std::vector<py::ssize_t>{(py::ssize_t)G.nj});
+  for (int a = 0; a < G.ni; a++) {
+    const int i = G.i0 + a * G.si;
+    ai.mutable_data()[a] = i;
+    ax.mutable_data()[a] = (double)((real)(i * dx_out) * (real)1.e3);
+  }
+  for (int b = 0; b < G.nj; b++) {
+    const int j = G.j0 + b * G.sj;
+    aj.mutable_data()[b] = j;
+    ay.mutable_data()[b] = (double)((real)(dy_out * j) * (real)1.e3);
+  }
+  py::array_t<bool> g(std::vector<py::ssize_t>{(py::ssize_t)G.ni, (py::ssize_t)G.nj});
+  for (size_t k = 0; k < gas.size(); k++) g.mutable_data()[k] = gas[k] != 0;
+  d["i"] = ai;
+  d["j"] = aj;
+  d["x"] = ax;
+  d["y"] = ay;
+  d["gas"] = g;
+}
+
 PYBIND11_MODULE(_hf2d, m) {
   m.doc() = "hf2d native runtime: OpenHyperFLOW2D-compatible DEEPS solver for AMD MI355X";
   m.attr("CELL_RECORD_BYTES") = (int)sizeof(CellRecord);
@@ -662,7 +709,35 @@ PYBIND11_MODULE(_hf2d, m) {
            py::arg("boxes") = py::none(), py::arg("cp_flow") = py::none(),
            "the wall nodes of the records (every node, or those of each box (x0, y0, dx, dy) in turn): i, j, x, y, "
            "flags, face_x, face_y, fric_x, fric_y, box_off and values [10, nnodes] in SURFACE_VARS order; cp_flow: "
-           "1-based flow index (default: the deck's Cp_Flow_Index)");
+           "1-based flow index (default: the deck's Cp_Flow_Index)")
+      .def("frame",
+           [](const Case& c, const std::vector<std::string>& vars, py::object region, std::pair<int, int> stride) {
+             // the frame rule over the records (frame_rule.hpp): what record_frames stores after a step
+             need_whole(c);
+             const Field& J = c.J;
+             const FrameGeom G = frame_geom("frame", frame_opts(vars, region, stride, 1, 1), J.nx, J.ny, (real)c.cfg.dx,
+                                            (real)c.cfg.dy, 0, J.nx, 0);
+             std::vector<real> vals((size_t)G.nvars * G.ncells());
+             auto gas = [&](int i, int j) { return frame_gas(J.at(i, j).CT); };
+             frame_eval(G, gas, [&](int i, int j, int v) {
+               const CellRecord& n = J.at(i, j);
+               return v == FV_P ? n.p : v == FV_T ? n.Tg : v == FV_RHO ? n.S[0] : v == FV_U ? n.U : n.V;
+             }, vals.data());
+             std::vector<uint8_t> g((size_t)G.ncells());
+             for (int a = 0; a < G.ni; a++)
+               for (int b = 0; b < G.nj; b++) g[(size_t)a * G.nj + b] = gas(G.i0 + a * G.si, G.j0 + b * G.sj) ? 1 : 0;
+             py::array_t<double> v(std::vector<py::ssize_t>{(py::ssize_t)G.nvars, (py::ssize_t)G.ni, (py::ssize_t)G.nj});
+             std::copy(vals.begin(), vals.end(), v.mutable_data());
+             py::dict d;
+             frame_table(d, c.cfg, G, g);
+             d["values"] = v;
+             return d;
+           },
+           py::arg("vars") = std::vector<std::string>(frame_var_names(), frame_var_names() + FRAME_NVARS),
+           py::arg("region") = py::none(), py::arg("stride") = std::pair<int, int>(1, 1),
+           "values [nvars, ni, nj] of the listed FRAME_VARS on the cells i0 + a si, j0 + b sj of the half-open region "
+           "(i0, i1, j0, j1) (default: the whole grid), with vars, i [ni], j [nj], x, y and gas [ni, nj]; gradients "
+           "use the immediate neighbours whatever the stride");
 
   m.def(
       "lean_tile_geom",
@@ -924,6 +999,34 @@ PYBIND11_MODULE(_hf2d, m) {
              return d;
            })
       .def("clear_surface", &SolverBase::clear_surface)
+      .def("record_frames",
+           [](SolverBase& s, const std::vector<std::string>& vars, py::object region, std::pair<int, int> stride, int every,
+              long capacity) { s.record_frames(frame_opts(vars, region, stride, every, capacity)); },
+           py::arg("vars") = std::vector<std::string>{"rho", "grad_rho"}, py::arg("region") = py::none(),
+           py::arg("stride") = std::pair<int, int>(1, 1), py::arg("every") = 1, py::arg("capacity") = 16,
+           "arm the per-step frame recorder: the listed FRAME_VARS on the cells i0 + a si, j0 + b sj of the region "
+           "(i0, i1, j0, j1) (None: the whole grid) after every `every`-th step, in a ring of `capacity` frames")
+      .def("frame_history",
+           [](SolverBase& s) {
+             FrameHistory H;
+             {
+               py::gil_scoped_release rel;
+               H = s.frame_history();
+             }
+             const FrameGeom& G = H.G;
+             const py::ssize_t n = (py::ssize_t)H.times.size();
+             py::array_t<double> t(std::vector<py::ssize_t>{n});
+             py::array_t<double> v(std::vector<py::ssize_t>{n, (py::ssize_t)G.nvars, (py::ssize_t)G.ni, (py::ssize_t)G.nj});
+             std::copy(H.times.begin(), H.times.end(), t.mutable_data());
+             std::copy(H.vals.begin(), H.vals.end(), v.mutable_data());
+             py::dict d;
+             d["times"] = t;
+             d["values"] = v;
+             d["total"] = H.total;
+             frame_table(d, s.cs.cfg, G, H.gas);
+             return d;
+           })
+      .def("clear_frames", &SolverBase::clear_frames)
       .def("start_averaging", &SolverBase::start_averaging, py::arg("every") = 1, py::arg("second_moments") = true,
            py::arg("step_weight") = false, py::arg("favre") = false, py::arg("species") = std::vector<int>{},
            "arm the whole-field accumulator: weighted running mean (and variances, U-V covariance) of "

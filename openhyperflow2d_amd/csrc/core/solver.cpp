@@ -498,6 +498,20 @@ const SurfacePlan& SolverBase::surface_plan() const {
 }
 void SolverBase::clear_surface() {}
 
+FrameGeom SolverBase::check_record_frames(const FrameOpts& o, int l_off) const {
+  const auto own = owned_columns();
+  const FrameGeom G = frame_geom("record_frames", o, cs.J.nx, cs.J.ny, (real)cs.cfg.dx, (real)cs.cfg.dy, own.first,
+                                 own.second, l_off - own.first);
+  if ((G.mask & FRAME_GRAD_MASK) && (comm->size() > 1 || own.first != 0 || own.second != cs.J.nx || !cs.J.whole()))
+    throw std::runtime_error("record_frames: this solver is one strip of several; the gradient variables of the "
+                             "per-step frame recorder need a one-process run (the rows of ghost columns are not "
+                             "maintained on every path)");
+  return G;
+}
+void SolverBase::record_frames(const FrameOpts&) { throw std::runtime_error("this backend has no per-step frame recorder"); }
+FrameHistory SolverBase::frame_history() { throw std::runtime_error("this backend has no per-step frame recorder"); }
+void SolverBase::clear_frames() {}
+
 void SolverBase::start_averaging(int, bool, bool, bool, const std::vector<int>&) {
   throw std::runtime_error("this backend has no flow-statistics accumulator");
 }
@@ -1007,6 +1021,7 @@ void CpuSolver::after_step() {
   if (load_cap) record_loads_step();
   if (wq_armed) record_wall_heat_step();
   if (sf_armed) record_surface_step();
+  if (fr_armed) record_frames_step();
   if (probe_cap == 0) return;
   const size_t np = probe_idx.size();
   const long slot = probe_total % probe_cap;
@@ -1169,6 +1184,52 @@ SurfaceHistory CpuSolver::surface_history() {
 const SurfacePlan& CpuSolver::surface_plan() const {
   if (!sf_armed) throw std::runtime_error("surface_history: no recorder armed (record_surface)");
   return sf_plan;
+}
+
+void CpuSolver::record_frames(const FrameOpts& o) {
+  // (a refused call throws here and leaves the armed recorder, if any, whole)
+  const FrameGeom G = check_record_frames(o, l_off);
+  fr_geom = G;
+  fr_opts = o;
+  fr.vals.assign((size_t)o.capacity * G.nvars * G.ncells(), 0.0);
+  fr.times.assign((size_t)o.capacity, 0.0);
+  fr_armed = true;
+  clear_frames();
+}
+
+void CpuSolver::clear_frames() {
+  if (fr_armed) fr.clear(0, fr_opts.every, true, (double)(cs.global_time + cur_time_part));
+}
+
+// the rule over the arrays download() would copy
+void CpuSolver::record_frames_step() {
+  const double t = (double)(cs.global_time + cur_time_part);
+  if (!stats_tick(fr.sc, t)) return;
+  const FrameGeom& G = fr_geom;
+  const real* p = lean_state ? P2[pbuf].data() : h.p.data();
+  const real* rows[FRAME_ROW] = {p, h.Tg[pbuf].data(), h.S[0].data(), h.U[pbuf].data(), h.V[pbuf].data()};
+  auto at = [&](int i, int j) { return (long)(i + G.ioff) * h.ny + j; };
+  const long slot = fr.total % fr_opts.capacity;
+  frame_eval(
+      G, [&](int i, int j) { return frame_gas(h.CT[at(i, j)]); }, [&](int i, int j, int v) { return rows[v][at(i, j)]; },
+      fr.vals.data() + (size_t)slot * G.nvars * G.ncells());
+  fr.times[slot] = t;
+  fr.total++;
+}
+
+FrameHistory CpuSolver::frame_history() {
+  if (!fr_armed) throw std::runtime_error("frame_history: no recorder armed (record_frames)");
+  FrameHistory H;
+  const FrameGeom& G = fr_geom;
+  H.G = G;
+  H.total = fr.total;
+  ring_oldest_first(fr.vals.data(), (size_t)G.nvars * G.ncells(), fr.times.data(), fr.total, fr_opts.capacity,
+                    [](double t) { return t; }, H.vals, H.times);
+  H.gas.resize((size_t)G.ncells());
+  for (int a = 0; a < G.ni; a++)
+    for (int b = 0; b < G.nj; b++)
+      H.gas[(size_t)a * G.nj + b] = frame_gas(h.CT[(long)(G.i0 + a * G.si + G.ioff) * h.ny + G.j0 + b * G.sj]) ? 1 : 0;
+  return H;
 }
 
 ProbeHistory CpuSolver::probe_history() {

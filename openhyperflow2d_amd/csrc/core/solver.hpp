@@ -25,6 +25,7 @@
 #include "load_plan.hpp"
 #include "wall_heat.hpp"
 #include "surface_plan.hpp"
+#include "frame_rule.hpp"
 
 namespace hf2d {
 
@@ -297,6 +298,21 @@ class SolverBase {
   // record_surface's checks: the options, and that this solver holds the whole field
   void check_record_surface(const SurfaceOpts& o) const;
 
+  // Opt-in per-step frame recorder (core/frame_rule.hpp): after every
+  // `every`-th step the armed variables of FRAME_VARS on the cells i0 + a si,
+  // j0 + b sj of the region, bit for bit what Case.frame gives on a field
+  // downloaded after that step, and the step's time go into a ring of
+  // `capacity` frames.  Arming again replaces the recorder and restarts the
+  // count.  A solver that is one strip of several records the row variables
+  // over the output columns it owns.  std::invalid_argument: frame_geom's.
+  // std::runtime_error: a stencil variable on a solver that is one strip of
+  // several, or a backend without a recorder.
+  virtual void record_frames(const FrameOpts& o);
+  virtual FrameHistory frame_history();
+  virtual void clear_frames();
+  // record_frames' checks and the geometry over the owned columns (l_off: local index of the first)
+  FrameGeom check_record_frames(const FrameOpts& o, int l_off) const;
+
  protected:
   // called by advance() after a step the host completed (not the device's asynchronous ones)
   virtual void after_step() {}
@@ -390,6 +406,16 @@ class CpuSolver : public SolverBase {
   void record_surface_step();       // after_step, while armed
   void sf_rebuild();                // upload(): the plan over the new records (another node count restarts the recorder)
   std::vector<real> sf_scratch;     // [SURFACE_PLANES][needed cells]
+
+  // host frame recorder: evaluates the rule on the arrays download() reads
+  void record_frames(const FrameOpts& o) override;
+  FrameHistory frame_history() override;
+  void clear_frames() override;
+  bool fr_armed = false;
+  FrameOpts fr_opts;
+  FrameGeom fr_geom;
+  SampledRing fr;                   // entries: [nvars][ni][nj]; no statistics
+  void record_frames_step();        // after_step, while armed
 
   HostArrays h;
   int gi0, gi1;     // owned global columns

@@ -197,6 +197,11 @@ struct DeviceSolver::Impl {
     DevArray<real> scratch;
     SampleRingMem ring;
   } surf_mem;
+  FrameDev frames{};           // per-step frame recorder (record_frames)
+  struct {
+    DevArray<real> scratch;
+    SampleRingMem ring;          // (stat stays empty: the frames keep no statistics)
+  } frames_mem;
   FlowStats stats{};           // whole-field statistics (start_averaging)
   size_t stats_planes = 0;     // planes of N doubles allocated behind stats.m
   size_t stats_used = 0;       // of which the armed options use (stats_plane_count)

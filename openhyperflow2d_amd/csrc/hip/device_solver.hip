@@ -18,8 +18,9 @@
 //                       (hf2d_lnm_*; lean_mech.hpp likewise)
 //   transport.hip       halo_kernels.hpp: halo pack / unpack, dt fold, xGMI
 //                       mailbox kernels (hf2d_p2p_*); RCCL and in-process transports
-//   observe.hip         monitors and the five per-step observers: probe_history.hpp,
-//                       load_history.hpp, wall_heat.hpp, surface_history.hpp (recorders),
+//   observe.hip         monitors and the six per-step observers: probe_history.hpp,
+//                       load_history.hpp, wall_heat.hpp, surface_history.hpp,
+//                       frame_history.hpp (recorders),
 //                       flow_stats.hpp (time-averaged flow statistics)
 //   device_knobs.hpp    the tuning knobs, one row each: members, environment reads,
 //                       Python attributes and mode_signature() are expanded from it
@@ -451,6 +452,7 @@ std::vector<StatsScalars*> DeviceSolver::tick_scalars() const {
   if (stats_armed) t.push_back(impl->stats.sc);
   if (wallq_armed) t.push_back(&impl->wallq.ring.sc->s);
   if (surf_armed) t.push_back(&impl->surf.ring.sc->s);
+  if (frames_armed) t.push_back(&impl->frames.ring.sc->s);
   return t;
 }
 
@@ -514,8 +516,8 @@ void DeviceSolver::download(Field& J) {
 // the plain sum of this cycle's dt -- bit for bit the CPU stepper's -- and not
 // the difference of two running sums (one ulp off after the first cycle
 // boundary).  Everything derived from time_part moves with it: the times the
-// four rings and the peak-time planes store (host_time() converts those of
-// earlier cycles as before) and the offsets of the three ticks' clocks (which
+// five rings and the peak-time planes store (host_time() converts those of
+// earlier cycles as before) and the offsets of the four ticks' clocks (which
 // go on unbroken).
 // Always called right after sync_scalars(), with no step in between:
 // last_dev_time is the device's time_part now.
@@ -531,6 +533,7 @@ void DeviceSolver::on_cycle_roll() {
   if (loads_live()) m.shift_times(m.loads.times, (size_t)m.loads.cap, T);
   if (wallq_live()) m.shift_ring(m.wallq.ring, (size_t)wallq_plan.nentries(), T);
   if (surf_live()) m.shift_ring(m.surf.ring, surf_plan.nentries(), T);
+  if (frames_live()) m.shift_ring(m.frames.ring, 0, T);   // (no statistics: the rows' times alone)
   for (StatsScalars* t : tick_scalars()) m.shift_clock(t, T);
   HIP_CHECK(hipStreamSynchronize(m.stream));
   m.sc_host->time_part = 0.0;
@@ -856,13 +859,14 @@ StepResult DeviceSolver::do_step_eager(const StepParams& P0, bool want_res) {
   if (!done.exchanged && (m.comm || m.local || m.p2p.on) && m.nranks > 1)
     exchange(lns_state ? CpuSolver::HALO_LNS : lean_state ? CpuSolver::HALO_LEAN : CpuSolver::HALO_STATE, c.slot_next);
   if (!cs.cfg.isAdiabaticWall) wall_heat(c);
-  if (probes_live() || stats_live() || loads_live() || wallq_live() || surf_live()) {
+  if (probes_live() || stats_live() || loads_live() || wallq_live() || surf_live() || frames_live()) {
     const PostStep v = post_step(c.slot, c.slot_next);
     if (probes_live()) launch_probe_record(P, v);
     if (stats_live()) launch_stats(P, v);
     if (loads_live()) launch_loads(P, v);
     if (wallq_live()) launch_wall_heat(P, v);
     if (surf_live()) launch_surface(P, v);
+    if (frames_live()) launch_frames(P, v);
   }
   nstep++;
   lns_prev_mu_t = P.fpa.is_mu_t;

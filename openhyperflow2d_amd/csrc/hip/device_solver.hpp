@@ -138,6 +138,12 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   SurfaceHistory surface_history() override;
   const SurfacePlan& surface_plan() const override;
   void clear_surface() override;
+  // per-step frame recorder (hip/frame_history.hpp): hf2d_wallq_tick,
+  // hf2d_frame_rows and hf2d_frame_store follow the step while armed; reading
+  // the history neither leaves the lean state nor changes a ping-pong parity
+  void record_frames(const FrameOpts& o) override;
+  FrameHistory frame_history() override;
+  void clear_frames() override;
   void trace_push(const char* name) override;
   void trace_pop() override;
   // the eligibility results, step counters, last tile launch and halo
@@ -267,7 +273,7 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   unsigned long long* tile_trace = nullptr;   // set only inside trace_tile
   std::vector<long> probe_idx_host;
   std::vector<real> probe_buf_host;
-  // The five observers.  Armed: the plan and the arrays exist.  A cached graph
+  // The six observers.  Armed: the plan and the arrays exist.  A cached graph
   // window bakes an observer's launches and arrays in, so arming, re-arming,
   // stopping or a plan rebuilt by upload() bumps observers_gen
   // (mode_signature: no window captured before replays after).  autotune()'s
@@ -294,12 +300,15 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   bool surf_friction = false;   // the armed plan holds friction terms (as loads_friction)
   SurfaceOpts surf_opts;        // what the plan is rebuilt from
   SurfacePlan surf_plan;        // host copy of the armed plan
+  bool frames_armed = false;
+  FrameOpts frames_opts;        // what the recorder was armed with (capacity: the ring's)
   // armed and not paused: the step launches the observer
   bool probes_live() const { return probe_cap > 0 && !observers_paused; }
   bool stats_live() const { return stats_on && !observers_paused; }
   bool loads_live() const { return loads_cap > 0 && !observers_paused; }
   bool wallq_live() const { return wallq_armed && !observers_paused; }
   bool surf_live() const { return surf_armed && !observers_paused; }
+  bool frames_live() const { return frames_armed && !observers_paused; }
   // the split fills store their gradients every step while a recorder reads them
   bool friction_recorded() const { return (loads_live() && loads_friction) || (surf_live() && surf_friction); }
   bool fx_pending = false;   // fused tile steps left the newest ghost columns and dt in the mailbox (p2p_complete)
@@ -329,6 +338,7 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void launch_loads(const StepParams& P, const PostStep& v);       // the load recorder's two launches
   void launch_wall_heat(const StepParams& P, const PostStep& v);   // the wall heat recorder's three launches
   void launch_surface(const StepParams& P, const PostStep& v);     // the surface recorder's three launches
+  void launch_frames(const StepParams& P, const PostStep& v);      // the frame recorder's three launches
   void lns_fill_views(SoA& sin, SoA& out) const;   // the views lns_materialize's fill would run over now
   int post_step_view(SoA& s) const;                // PR_* kind and view of the post-step buffers
   // A recorder's plan over the records the backend holds now (throws where a
@@ -342,7 +352,7 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   void refuse_wall_nodes(const std::string& who, const char* nodes, bool wall_T) const;   // the two rules that refuse such a plan
   void plans_rebuild();                   // upload() replaced the records under the armed recorders
   double host_time(double t_dev) const;   // the host's time of a stored DevScalars::time_part
-  std::vector<StatsScalars*> tick_scalars() const;   // device scalars of every armed tick: accumulator, wall heat, surface
+  std::vector<StatsScalars*> tick_scalars() const;   // device scalars of every armed tick: accumulator, wall heat, surface, frames
   uint64_t mode_signature() const;   // kernel-selecting state (graph windows replay only under the same)
   // One step (do_step_eager): the kernels that run it, what every path reads
   // of the step, and what a path reports to the common tail.

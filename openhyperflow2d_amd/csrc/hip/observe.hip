@@ -1,13 +1,15 @@
 // Observers of the run: monitor points, the per-step probe recorder
 // (probe_history.hpp), the per-step load recorder (load_history.hpp), the
 // per-step wall heat recorder (wall_heat.hpp), the per-step surface recorder
-// (surface_history.hpp) and the time-averaged flow statistics (flow_stats.hpp).
+// (surface_history.hpp), the per-step frame recorder (frame_history.hpp) and the
+// time-averaged flow statistics (flow_stats.hpp).
 
 #include "device_impl.hpp"
 #include "flow_stats.hpp"
 #include "load_history.hpp"
 #include "wall_heat.hpp"
 #include "surface_history.hpp"
+#include "frame_history.hpp"
 
 namespace hf2d {
 
@@ -265,7 +267,7 @@ void DeviceSolver::refuse_wall_nodes(const std::string& who, const char* nodes, 
                                                   "TurbStartIter has passed; arm (or upload) later");
   // a plain lean tile step stores no T, and T = p / R / rho holds only where R
   // does not change over the step; the tile kernel runs its output variant for
-  // the probe recorder and the accumulator alone (step_tile.hip)
+  // the probe recorder, the accumulator and the frame recorder alone (step_tile.hip)
   if (wall_T && lean_ok && !lean_sg_ok && make_params(last_iter + iter).chem_model != NO_REACTIONS)
     throw std::runtime_error(who + ": a reacting gas mixture on the lean inviscid step stores no wall temperature between "
                                    "outputs; the recorder cannot be armed on this deck");
@@ -566,6 +568,92 @@ void DeviceSolver::launch_surface(const StepParams& P, const PostStep& v) {
   // (at least one workgroup: the sample's time is written for a plan without nodes too)
   const long gn = L.nnodes > 0 ? (L.nnodes + SURF_BLOCK - 1) / SURF_BLOCK : 1;
   hipLaunchKernelGGL(hf2d_surf_nodes, dim3((unsigned)gn), dim3(SURF_BLOCK), 0, m.stream, L, m.sc);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Per-step frame recorder (hip/frame_history.hpp)
+// ---------------------------------------------------------------------------
+// No plan: the kernels read CT live, so upload() rebuilds nothing.
+void DeviceSolver::record_frames(const FrameOpts& o) {
+  // (a refused call throws here and leaves the armed recorder, if any, whole)
+  const FrameGeom G = check_record_frames(o, l_off);
+  Impl& m = *impl;
+  flush_pending();
+  p2p_complete();
+  HIP_CHECK(hipSetDevice(dev));
+  HIP_CHECK(hipDeviceSynchronize());   // (the steps flush_pending launched: nothing in flight reads the arrays)
+  frames_armed = false;
+  FrameDev& L = m.frames;
+  auto& a = m.frames_mem;
+  SampleRing& r = L.ring;
+  const int cap = (int)std::min<long>(o.capacity, 0x7fffffffL);
+  r.vals = m.grown(a.ring.vals, (size_t)cap * G.nvars * G.ncells());
+  r.times = m.grown(a.ring.times, (size_t)cap);
+  r.sc = m.grown(a.ring.sc, 1);
+  r.stat = nullptr;
+  r.cap = cap;
+  r.statistics = 0;
+  L.scratch = m.grown(a.scratch, (size_t)FRAME_ROW * G.nbox());
+  L.G = G;
+  frames_opts = o;
+  frames_opts.capacity = cap;
+  m.ring_reset(r, 0, o.every, true, time_offset);
+  frames_armed = true;
+  observers_gen++;
+}
+
+void DeviceSolver::clear_frames() {
+  if (!frames_armed) return;
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  impl->ring_reset(impl->frames.ring, 0, frames_opts.every, true, time_offset);
+  observers_gen++;
+}
+
+FrameHistory DeviceSolver::frame_history() {
+  if (!frames_armed) throw std::runtime_error("frame_history: no recorder armed (record_frames)");
+  flush_pending();
+  HIP_CHECK(hipSetDevice(dev));
+  Impl& m = *impl;
+  const FrameDev& L = m.frames;
+  const FrameGeom& G = L.G;
+  const size_t ne = (size_t)G.nvars * G.ncells();
+  WallHeatScalars ws;
+  std::vector<real> vals((size_t)L.ring.cap * ne);
+  std::vector<double> tp((size_t)L.ring.cap);
+  HIP_CHECK(hipMemcpyAsync(&ws, L.ring.sc, sizeof ws, hipMemcpyDeviceToHost, m.stream));
+  if (!vals.empty())
+    HIP_CHECK(hipMemcpyAsync(vals.data(), L.ring.vals, vals.size() * sizeof(real), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipMemcpyAsync(tp.data(), L.ring.times, tp.size() * sizeof(double), hipMemcpyDeviceToHost, m.stream));
+  HIP_CHECK(hipStreamSynchronize(m.stream));
+  FrameHistory H;
+  H.G = G;
+  H.total = (long)ws.s.samples;
+  ring_oldest_first(vals.data(), ne, tp.data(), H.total, (long)L.ring.cap, [&](double t) { return host_time(t); },
+                    H.vals, H.times);
+  H.gas.resize((size_t)G.ncells());
+  for (int a = 0; a < G.ni; a++)
+    for (int b = 0; b < G.nj; b++)
+      H.gas[(size_t)a * G.nj + b] = frame_gas(h.CT[(long)(G.i0 + a * G.si + G.ioff) * h.ny + G.j0 + b * G.sj]) ? 1 : 0;
+  return H;
+}
+
+void DeviceSolver::launch_frames(const StepParams& P, const PostStep& v) {
+  Impl& m = *impl;
+  const FrameDev& L = m.frames;
+  hipLaunchKernelGGL(hf2d_wallq_tick, dim3(1), dim3(64), 0, m.stream, L.ring.sc, m.sc, L.ring.cap);
+  HIP_CHECK(hipGetLastError());
+  if (L.G.nbox() > 0) {
+    const dim3 g((unsigned)((L.G.nbox() + FRAME_BLOCK - 1) / FRAME_BLOCK)), b(FRAME_BLOCK);
+    with_kind(v.kind, [&](auto K) {
+      hipLaunchKernelGGL(hf2d_frame_rows<decltype(K)::value>, g, b, 0, m.stream, P, v.s, L);
+    });
+    HIP_CHECK(hipGetLastError());
+  }
+  // (at least one workgroup: the sample's time is written for a strip without output columns too)
+  const long gn = L.G.ncells() > 0 ? (L.G.ncells() + FRAME_BLOCK - 1) / FRAME_BLOCK : 1;
+  hipLaunchKernelGGL(hf2d_frame_store, dim3((unsigned)gn), dim3(FRAME_BLOCK), 0, m.stream, L, v.s.CT, v.s.N, m.sc);
   HIP_CHECK(hipGetLastError());
 }
 

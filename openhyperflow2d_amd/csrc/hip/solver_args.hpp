@@ -1,6 +1,6 @@
 // Plain argument blocks and constants of the lean N-S step (lean_ns.hpp), the
 // lean mechanism step (lean_mech.hpp) and the per-step observers (probe, load,
-// wall heat and surface recorders; their post-step view and kind dispatch):
+// wall heat, surface and frame recorders; their post-step view and kind dispatch):
 // what DeviceSolver::Impl and the host code of every unit need of them, without
 // the families' device code.
 #pragma once
@@ -10,6 +10,7 @@
 #include "../core/lean_euler.hpp"
 #include "../core/wall_heat.hpp"
 #include "../core/surface_plan.hpp"
+#include "../core/frame_rule.hpp"
 
 namespace hf2d {
 
@@ -183,6 +184,15 @@ struct SurfaceDev {
   long ncells = 0, nnodes = 0;
   real* scratch = nullptr;         // [SURFACE_PLANES][ncells] the needed cells' values after the step
   SampleRing ring;
+};
+
+// Per-step frame recorder (frame_history.hpp): the geometry, the rows of its
+// box and the ring (no statistics); the tick's scalars are the wall heat
+// recorder's kind, its own
+struct FrameDev {
+  FrameGeom G;
+  real* scratch = nullptr;         // [FRAME_ROW][G.nbox()] the rows of the box's gas cells after the step
+  SampleRing ring;                 // vals: [cap][nvars][ni][nj]
 };
 
 }  // namespace hf2d

@@ -152,7 +152,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
   // not store: where R is constant over a tile step (single gas, or no
   // reactions) the recorder forms it from p, R, rho; a reacting mixture
   // runs the output variant instead
-  const bool rec_out = (probes_live() || stats_live()) && !sg && P.chem_model != NO_REACTIONS;
+  const bool rec_out = (probes_live() || stats_live() || frames_live()) && !sg && P.chem_model != NO_REACTIONS;
   const bool out = step_outputs || want_res || rec_out;
   // staggered start only for a grid that is resident at once (<= 4 dispatch
   // rounds: measured 1.5 us faster on the headline grid; the 4000x1000 triple

@@ -48,6 +48,8 @@ PROBE_VARS = ("p", "T", "rho", "U", "V")   # column order of Simulation.probe_hi
 LOAD_PARTS = ("Fx_p", "Fx_d", "Fy_p", "Fy_d")   # last axis of Simulation.load_history()["forces"]
 # row order of Case.surface()["values"] and of Simulation.surface_history()["values"]
 SURFACE_VARS = ("p", "Cp", "T", "tau_x", "tau_y", "Cf_x", "Cf_y", "q_y", "q_x", "St")
+# variables of Case.frame() and of Simulation.record_frames()
+FRAME_VARS = ("p", "T", "rho", "U", "V", "grad_rho", "grad_p", "vorticity", "dilatation", "ducros")
 WALL_HEAT_X = ("Q", "Alpha", "Cp", "St")   # rows of Case.heat_flux_x() and of Simulation.wall_heat_history()["x"]
 
 
@@ -285,6 +287,68 @@ class Simulation:
     def clear_surface(self) -> None:
         """Empty the ring and the statistics; the recorder stays armed."""
         self.solver.clear_surface()
+
+    # -- per-step frame recorder -----------------------------------------------
+    def record_frames(self, vars=("rho", "grad_rho"), region=None, stride=(1, 1), every: int = 1,
+                      capacity: int = 16) -> None:
+        """Arm the per-step frame recorder: a sequence of fields at a fixed
+        step cadence (a schlieren movie), ``vars`` out of ``FRAME_VARS = ("p",
+        "T", "rho", "U", "V", "grad_rho", "grad_p", "vorticity", "dilatation",
+        "ducros")``.
+
+        ``region = (i0, i1, j0, j1)`` is half-open and defaults to the whole
+        grid; the output cells are ``i0 + a * stride[0]``, ``j0 + b *
+        stride[1]``.  From now on every ``every``-th step appends one frame
+        ``[nvars, ni, nj]`` and the step's time to a ring of ``capacity``
+        frames kept by the backend.  The first five variables are the probe
+        recorder's row, bit for bit ``field(name)`` after that step.  The
+        other five are differences of the rows of the cell and its immediate
+        gas neighbours (whatever the stride; gas: set and not solid), central
+        with both neighbours of a direction, one-sided with one, ``+0`` with
+        none::
+
+            ddx(q) = (q_E - q_W) * ((1 / dx) / max(hasW + hasE, 1))     # ddy likewise
+            grad_rho   = sqrt(ddx(rho)**2 + ddy(rho)**2)                # grad_p likewise
+            vorticity  = ddx(V) - ddy(U)
+            dilatation = ddx(U) + ddy(V)
+            ducros     = dilatation**2 / ((dilatation**2 + vorticity**2) + 1e-30)
+
+        Every value is bit for bit ``case.frame(vars, region, stride)`` on a
+        field downloaded after that step; a cell that is not gas reads
+        ``+0.0``.  Axisymmetric decks use the same planar expressions (no
+        ``V / y`` term).  On the GPU three small kernels run at the end of each
+        step, inside the step graphs, and the lean states are never
+        materialised.  Arming again replaces the recorder; a refused call
+        leaves an armed one as it was.  ``ValueError``: an unknown, repeated
+        or empty ``vars``, a region that is empty or outside the grid, a
+        stride below 1, ``every < 1``, ``capacity < 1``, a ring of more than
+        2^31 entries.  A solver that is one strip of several records the
+        first five variables over the output columns it owns and refuses the
+        other five (``RuntimeError``)."""
+        if isinstance(vars, str):
+            vars = (vars,)
+        r = None if region is None else [int(v) for v in region]
+        if r is not None and len(r) != 4:
+            raise ValueError("record_frames: a region is (i0, i1, j0, j1)")
+        si, sj = stride
+        self.solver.record_frames([str(v) for v in vars], r, (int(si), int(sj)), int(every), int(capacity))
+
+    def frame_history(self) -> dict:
+        """The recorded frames, oldest first: ``times`` [n] (the clock of
+        ``probe_history()``), ``values`` [n, nvars, ni, nj] (float64), ``total``
+        (samples taken since arming; n = min(total, capacity)), ``vars``, and
+        the static ``i`` [ni], ``j`` [nj] (the output cells; on a strip the
+        owned global columns of the region), ``x`` [ni], ``y`` [nj] (the field
+        dump's coordinates) and ``gas`` [ni, nj].  Reading does not disturb
+        the solver state."""
+        h = dict(self.solver.frame_history())
+        for k, v in h.items():
+            h[k] = int(v) if k == "total" else tuple(str(s) for s in v) if k == "vars" else np.asarray(v)
+        return h
+
+    def clear_frames(self) -> None:
+        """Empty the ring; the recorder stays armed."""
+        self.solver.clear_frames()
 
     # -- time-averaged flow statistics ---------------------------------------
     def start_averaging(self, every: int = 1, second_moments: bool = True, weight: str = "time",
