@@ -759,6 +759,73 @@ PYBIND11_MODULE(_hf2d, m) {
   m.def("lean_tile_stage_kmax", &lean_tile_stage_kmax, py::arg("nt"), py::arg("cpt"),
         "largest slots per thread (ceil(NC / nt)) the single-gas lean tile kernel stages in one batch of loads; "
         "beyond it the kernel runs the staging loop (lean_tile_last['stage'] == 0)");
+  m.def(
+      "air_table_build",
+      [](const std::vector<double>& x, const std::vector<double>& y, const std::vector<double>& R) {
+        if (x.size() != y.size() || x.size() > (size_t)MAX_TABLE_PTS || R.size() != (size_t)NSPEC)
+          throw std::runtime_error("air_table_build: x, y of equal length <= 64 and 4 gas constants expected");
+        SpeciesProps sp;
+        for (int s = 0; s < NSPEC; s++) sp.R[s] = (real)R[s];
+        TableData& t = sp.Cp[H_AIR];
+        t.n = (int)x.size();
+        for (int k = 0; k < t.n; k++) {
+          t.x[k] = x[k];
+          t.y[k] = y[k];
+        }
+        const AirTable a = air_table_build(sp);
+        py::dict d;
+        d["n"] = a.n;
+        d["mode"] = a.mode;
+        d["R"] = (double)a.R;
+        d["x"] = std::vector<double>(a.x, a.x + AIR_TABLE_PTS);
+        d["y"] = std::vector<double>(a.y, a.y + AIR_TABLE_PTS);
+        d["bytes"] = (int)sizeof(AirTable);
+        return d;
+      },
+      py::arg("x"), py::arg("y"), py::arg("R") = std::vector<double>{0.0, 0.0, 0.0, 287.0},
+      "the block the single-gas lean tile kernels keep in LDS for the Cp_air table (x, y) and the gas constants R "
+      "(fu, ox, cp, air): n, mode (1: evaluated from LDS, 0: table_eval on the species pack), R and the padded "
+      "knots / values (common.hpp AirTable); needs no GPU");
+  m.def(
+      "air_table_probe",
+      [](const std::vector<double>& x, const std::vector<double>& y, const std::vector<double>& xv) {
+        auto r = air_table_probe(x, y, xv);
+        return py::make_tuple(r.first, r.second);
+      },
+      py::arg("x"), py::arg("y"), py::arg("xv"),
+      "Cp_air at up to 64 values xv, evaluated on the GPU the way the single-gas lean tile kernels do; (values, mode)");
+  m.def(
+      "air_table_eval",
+      [](const std::vector<double>& x, const std::vector<double>& y, const std::vector<double>& xv) {
+        if (x.size() != y.size() || x.size() > (size_t)MAX_TABLE_PTS) throw std::runtime_error("air_table_eval: table size");
+        SpeciesProps sp;
+        TableData& t = sp.Cp[H_AIR];
+        t.n = (int)x.size();
+        for (int k = 0; k < MAX_TABLE_PTS; k++) {
+          t.x[k] = k < t.n ? x[k] : 0.0;
+          t.y[k] = k < t.n ? y[k] : 0.0;
+        }
+        const AirTable a = air_table_build(sp);
+        std::vector<double> out;
+        for (const double v : xv) out.push_back((double)(a.mode ? air_table_eval(a, (real)v) : table_eval(t, (real)v)));
+        return py::make_tuple(out, a.mode);
+      },
+      py::arg("x"), py::arg("y"), py::arg("xv"),
+      "air_table_probe's evaluation compiled for the host (air_table_eval on the AirTable in mode 1): (values, mode)");
+  m.def("table_eval",
+        [](const std::vector<double>& x, const std::vector<double>& y, const std::vector<double>& xv) {
+          if (x.size() != y.size() || x.size() > (size_t)MAX_TABLE_PTS) throw std::runtime_error("table_eval: table size");
+          TableData t;
+          t.n = (int)x.size();
+          for (int k = 0; k < MAX_TABLE_PTS; k++) {
+            t.x[k] = k < t.n ? x[k] : 0.0;
+            t.y[k] = k < t.n ? y[k] : 0.0;
+          }
+          std::vector<double> out;
+          for (const double v : xv) out.push_back((double)table_eval(t, (real)v));
+          return out;
+        },
+        py::arg("x"), py::arg("y"), py::arg("xv"), "the host's table_eval (common.hpp) of the table (x, y) at every xv");
   m.def("sk_eligible", [](const Case& c) { std::string w; const int md = sk_eligible(c, &w); return py::make_tuple(md, w); },
         py::arg("case"), "split-kernel specialisation (0 generic, 1 single-gas laminar, 2 single-gas turbulent; reason)");
   m.def("smooth", [](py::array_t<double, py::array::c_style> a, int axis) {
@@ -1377,6 +1444,7 @@ PYBIND11_MODULE(_hf2d, m) {
                                d["seen"] = t.seen;
                                d["dt_read"] = t.dt_read;
                                d["stage"] = t.stage;
+                               d["table"] = t.table;
                                return d;
                              },
                              "geometry and variant (0 plain, 1 outputs, 2 residual) of the last lean tile launch; "

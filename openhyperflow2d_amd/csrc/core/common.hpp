@@ -309,4 +309,73 @@ struct SpeciesProps {
   real M[NSPEC] = {0, 0, 0, 0};   // molar masses from R_s (kg/mol)
 };
 
+// What chemistry_single_gas() needs of a SpeciesProps, prepared once on the
+// host for the device's single-gas tile kernels (lean_tile.hpp), which copy
+// it into LDS with the tile: the knots and values of Cp[H_AIR] padded to a
+// fixed capacity (x with +inf past the last knot, y with +0) and the mixture
+// constant R.  AIR_TABLE_WORDS 8-byte words; x / y double in every build, as
+// in TableData.
+// mode 1 (fast): 2 <= n <= AIR_TABLE_PTS and x non-decreasing, the tables the
+// branch-free segment search of air_table_eval() is exact for.  mode 0: the
+// kernel evaluates table_eval() on the SpeciesProps itself (n <= 1, more
+// points than the capacity, a knot below its predecessor or a NaN knot);
+// x / y then hold the padding only.
+constexpr int AIR_TABLE_PTS = 16;
+struct AirTable {
+  int n = 0;
+  int mode = 0;
+  real R = 0;
+#ifdef HF2D_FP32
+  float R_pad = 0;   // (R keeps a whole word)
+#endif
+  double x[AIR_TABLE_PTS];
+  double y[AIR_TABLE_PTS];
+};
+constexpr int AIR_TABLE_WORDS = 2 + 2 * AIR_TABLE_PTS;
+static_assert(sizeof(AirTable) == AIR_TABLE_WORDS * 8, "AirTable is staged word by word");
+
+inline AirTable air_table_build(const SpeciesProps& sp) {
+  AirTable a;
+  const TableData& t = sp.Cp[H_AIR];
+  a.n = t.n;
+  // (the expression of chemistry_single_gas)
+  a.R = ((sp.R[H_FU] * 0. + sp.R[H_OX] * 0.) + sp.R[H_CP] * 0.) + sp.R[H_AIR] * 1.;
+  bool ok = t.n >= 2 && t.n <= AIR_TABLE_PTS;
+  for (int k = 1; ok && k < t.n; k++) ok = t.x[k] >= t.x[k - 1];
+  a.mode = ok ? 1 : 0;
+  for (int k = 0; k < AIR_TABLE_PTS; k++) {
+    a.x[k] = ok && k < t.n ? t.x[k] : __builtin_inf();
+    a.y[k] = ok && k < t.n ? t.y[k] : 0.0;
+  }
+  return a;
+}
+// table_eval() of the table a mode-1 AirTable holds, without a loop of
+// data-dependent length: for non-decreasing knots the scan's segment is
+//   i = min(1 + #{k >= 1 : xv >= x[k]}, n - 1)
+// (the +inf padding counts only for xv = +inf, which the min clamps like every
+// xv >= x[n-1]), except at xv <= x[0], where the scan answers 1 whatever the
+// knots: the two differ for xv == x[0] == x[1].  A NaN xv counts nothing,
+// takes segment 1 and gives a NaN.  The knot reads do not depend on each
+// other (from LDS: broadcast reads, all in flight at once); the interpolation
+// is table_eval's expression.
+HF_HD inline real air_table_eval(const AirTable& t, real xv) {
+  const int n = t.n;
+  int i = 1;
+#pragma unroll
+  for (int k = 1; k < AIR_TABLE_PTS; k++) i += xv >= t.x[k] ? 1 : 0;
+  i = i < n - 1 ? i : n - 1;
+  if (xv <= t.x[0]) i = 1;
+  return t.y[i] + hf_div((t.y[i - 1] - t.y[i]) * (xv - t.x[i]), t.x[i - 1] - t.x[i]);
+}
+
+// The device solver's copy of the species pack with its prepared block behind
+// it (StepParams::species points at sp; no kernel argument of its own).
+struct SpeciesDev {
+  SpeciesProps sp;
+  AirTable air;
+};
+HF_HD inline const AirTable* air_table_of(const SpeciesProps* sp) {
+  return &reinterpret_cast<const SpeciesDev*>(sp)->air;
+}
+
 }  // namespace hf2d

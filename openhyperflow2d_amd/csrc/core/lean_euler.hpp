@@ -183,6 +183,11 @@ struct LeanIOCommon {
   HF_HD real dyU(int k) const { return L.dSdy_in[k * N + iU]; }
   HF_HD real dyD(int k) const { return L.dSdy_in[k * N + iD]; }
   HF_HD real beta(int k) const { return obeta[k]; }
+  // chemistry_single_gas() of the node (TileIO: from the tile's AirTable)
+  template <class CN>
+  HF_HD void single_gas(CN& n, const SpeciesProps& sp) const {
+    chemistry_single_gas(n, sp);
+  }
   HF_HD real Src(int) const { return 0.0; }
   HF_HD real SrcAdd(int k) const { return noslip ? L.SrcAdd[k * N + idx] : 0.0; }
   HF_HD void put_S(int k, real v) { sm[k] = v; }
@@ -270,13 +275,30 @@ struct LeanChemNode {
 // chemistry_zeldovich() evaluated for a node whose species partial densities
 // are +0: Y = (0, 0, 0, 1), R = R_air, Cp = Cp_air(T) (each zero-fraction term
 // of the mixture sums is +0, so the sums reduce to the air term exactly).
-// (A copy of the air Cp table in the kernel arguments, scanned branch-free,
-// cost 95 SGPR spills in the tile kernel and ~9 % of its time: measured and
-// removed.)
+// On the device table_eval() through the species pointer is a chain of
+// dependent global loads per cell (n and R; x[0]; x[n-1]; two per pass of the
+// scan, which runs as long as the wave's slowest lane; the four operands),
+// every wait of which also drains the stores the predictor has just issued.
+// The single-gas tile kernels therefore carry the table in LDS
+// (chemistry_single_gas_lds: AirTable, staged with the tile, lean_tile.hpp).
+// (A copy of the air Cp table in the kernel arguments instead, scanned
+// branch-free, cost 95 SGPR spills in the tile kernel and ~9 % of its time:
+// measured and removed; that was the SGPR pressure of 32 more argument
+// words, not the table search.)
 template <class N>
 HF_HD inline void chemistry_single_gas(N& n, const SpeciesProps& sp) {
   n.R = ((sp.R[H_FU] * 0. + sp.R[H_OX] * 0.) + sp.R[H_CP] * 0.) + sp.R[H_AIR] * 1.;
   n.CP = table_eval(sp.Cp[H_AIR], n.Tg) * 1.;
+  n.Y[0] = n.Y[1] = n.Y[2] = 0.;
+  n.Y[3] = 1.;
+}
+// The same from the prepared block of a table in mode 1 (R and the padded
+// knots, air_table_build): same bits for every Tg but a NaN, which gives a
+// NaN here too.
+template <class N>
+HF_HD inline void chemistry_single_gas_lds(N& n, const AirTable& t) {
+  n.R = t.R;
+  n.CP = air_table_eval(t, n.Tg) * 1.;
   n.Y[0] = n.Y[1] = n.Y[2] = 0.;
   n.Y[3] = 1.;
 }
@@ -413,7 +435,7 @@ HF_HD inline real lean_cell(const StepParams& P, const LeanSoA& L, IO& io, const
         c.CT = CT;
         c.lam = c.mu = 0.;
         if (SG)
-          chemistry_single_gas(c, *P.species);
+          io.single_gas(c, *P.species);
         else
           chemistry_zeldovich(c, *P.species, P.sm, P.chem_model);
         if (c.R != own.R) io.out_R(c.R);   // constant for a frozen mixture
@@ -456,6 +478,10 @@ struct LeanTile {
   // device single-gas kernels: slots per thread of the batched staging
   // (lean_tile.hpp), 0: the loop of lean_tile_stage
   int stage = 0;
+  // device single-gas kernels: 1: the tile carries the species pack's
+  // AirTable in LDS and Cp_air is evaluated from it (AirTable::mode, chosen
+  // by the host); 0: table_eval on the species pack in global memory
+  int table = 0;
 };
 
 // Tile height: tj > 0 overrides (clamped to [LEAN_TILE_MIN_TJ, block]);
@@ -527,6 +553,14 @@ struct TileIO : LeanIOCommon {
   HF_HD TileIO(const LeanSoA& l, long i, const real* s, int nc, int w, int cc)
       : LeanIOCommon(l, i), lds(s), NC(nc), W(w), c(cc), cL(cc), cR(cc), cU(cc), cD(cc) {}
   HF_HD real at(int f, int cc) const { return lds[f * NC + cc]; }
+  // the tile's AirTable (device single-gas kernels, LeanTile::table != 0)
+  const AirTable* tab = nullptr;
+  int table = 0;
+  template <class CN>
+  HF_HD void single_gas(CN& n, const SpeciesProps& sp) const {
+    if (SG && table) chemistry_single_gas_lds(n, *tab);
+    else chemistry_single_gas(n, sp);
+  }
   HF_HD real U0() const { return at(FU, c); }
   HF_HD real V0() const { return at(FV, c); }
   HF_HD real P0() const { return at(FP, c); }

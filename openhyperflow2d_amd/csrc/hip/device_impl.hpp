@@ -130,7 +130,8 @@ struct DeviceSolver::Impl {
   unsigned* chem_count = nullptr;
   real *Ys[2] = {nullptr, nullptr}, *As = nullptr, *Bs = nullptr, *Fs = nullptr, *betas = nullptr;
   real *dSdxs[2] = {nullptr, nullptr}, *dSdys[2] = {nullptr, nullptr};
-  SpeciesProps* species = nullptr;
+  SpeciesProps* species = nullptr;   // (the sp of a SpeciesDev: air_table_of)
+  SpeciesDev species_host;           // what upload() copied there
   ScenarioTables* scen = nullptr;
   long* probe_idx = nullptr;   // K8 monitor probes (sample_monitors)
   real* probe_out = nullptr;

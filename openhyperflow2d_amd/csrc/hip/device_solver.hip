@@ -161,7 +161,7 @@ DeviceSolver::DeviceSolver(Case& c, int device, int gi0_, int gi1_) : SolverBase
         m.dSdys[b] = m.mem.alloc<real>(n);
       }
   }
-  m.species = m.mem.alloc<SpeciesProps>(1);
+  m.species = &m.mem.alloc<SpeciesDev>(1)->sp;   // (with its AirTable: air_table_of)
   m.scen = m.mem.alloc<ScenarioTables>(1);
   m.sc = m.mem.alloc<DevScalars>(1);
   HIP_CHECK(hipHostMalloc((void**)&m.sc_host, sizeof(DevScalars), hipHostMallocDefault));
@@ -378,7 +378,14 @@ void DeviceSolver::upload() {
   }
   lean_state = 0;
   cp(m.wslot, h.wslot.data(), N * sizeof(int32_t));
-  cp(m.species, &cs.cfg.species, sizeof(SpeciesProps));
+  {
+    // the species pack and, rebuilt with every upload of it, its AirTable
+    SpeciesDev& sd = m.species_host;
+    sd.sp = cs.cfg.species;
+    sd.air = air_table_build(sd.sp);
+    cp(m.species, &sd, sizeof(SpeciesDev));
+    air_table_mode = sd.air.mode;
+  }
   if (h.mech) {
     h.mech_from_case(cs, gi0 - l_off);
     const size_t YB = (size_t)m.nsp * N * sizeof(real);
@@ -575,10 +582,10 @@ std::string DeviceSolver::profile_path_facts() const {
                 "\"fp\": %d, \"sk_mode\": %d, \"split_mode\": %d, \"lean_ok\": %s, \"lean_sg_ok\": %s, \"lns_ok\": %s, \"lns_turb\": %d, "
                 "\"lns_steps\": %ld, \"lnm_steps\": %ld, \"graph_captures\": %ld, \"graph_launches\": %ld, "
                 "\"lean_tile_last\": {\"nt\": %d, \"cpt\": %d, \"TI\": %d, \"TJ\": %d, \"nbi\": %d, \"nbj\": %d, "
-                "\"fx\": %d, \"var\": %d, \"seen\": %d}, ",
+                "\"fx\": %d, \"var\": %d, \"seen\": %d, \"table\": %d}, ",
                 (int)(8 * sizeof(real)), sk_mode, split_mode(), lean_ok ? "true" : "false", lean_sg_ok ? "true" : "false",
                 lns_ok ? "true" : "false", lns_turb, lns_steps, lnm_steps, graph_captures, graph_launches, t.nt, t.cpt,
-                t.TI, t.TJ, t.nbi, t.nbj, t.fx, t.var, t.seen);
+                t.TI, t.TJ, t.nbi, t.nbj, t.fx, t.var, t.seen, t.table);
   return std::string(b) + "\"lean_why\": " + quoted(lean_why) + ", \"lns_why\": " + quoted(lns_why) +
          ", \"transport\": " + quoted(halo_transport());
 }

@@ -25,6 +25,12 @@ bool gpu_available();
 // nt threads and cpt cells per thread stages in one batch (lean_tile.hpp); a
 // tile that needs more runs the staging loop.  0: no such kernel.
 int lean_tile_stage_kmax(int nt, int cpt);
+// Cp_air at up to 64 values xv for the table (x, y), evaluated on the device
+// the way the single-gas lean tile kernels do (AirTable built by
+// air_table_build, staged into LDS, air_table_eval; table_eval on the pack
+// for a table in mode 0); returns the values and the mode.
+std::pair<std::vector<double>, int> air_table_probe(const std::vector<double>& x, const std::vector<double>& y,
+                                                    const std::vector<double>& xv);
 
 // In-process stand-in for the RCCL communicator: N DeviceSolvers (one host
 // thread each, possibly sharing one GPU) exchange halo buffers with D2D
@@ -229,13 +235,16 @@ class DeviceSolver : public SolverBase, public DeviceKnobs {
   // the unbroken run of tile steps with this nt and cpt that the last one
   // ends (the last step of a host call is never a plain one); dt_read: how
   // it read the step's dt (StepParams::dt_read); stage: slots per thread of
-  // the batched staging, 0 for the staging loop (LeanTile::stage).  Tests
-  // assert through it which variant ran.
+  // the batched staging, 0 for the staging loop (LeanTile::stage); table: 1
+  // where it evaluated Cp_air from the AirTable in LDS, 0 where it ran
+  // table_eval on the species pack (LeanTile::table).  Tests assert through
+  // it which variant ran.
   struct TileLast {
     int nt = 0, cpt = 0, TI = 0, TJ = 0, nbi = 0, nbj = 0, stagger = 0, fx = 0, var = 0, seen = 0, dt_read = 0;
-    int stage = 0;
+    int stage = 0, table = 0;
   };
   TileLast lean_tile_last;
+  int air_table_mode = 0;   // AirTable::mode of the uploaded species pack
 
   // ---- counters ----
   long nstep = 0;

@@ -136,6 +136,25 @@ __device__ __forceinline__ void lean_stage_write(const LeanTile& T, const LeanSt
       for (int f = 0; f < LEAN_TILE_FIELDS_SG; f++) lds[f * T.NC + s.c[k]] = s.v[k][f];
 }
 
+// The species pack's AirTable in a single-gas tile's LDS, behind the staged
+// fields at the next 8-byte boundary: thread t < AIR_TABLE_WORDS carries word
+// t.  The load has no condition (threads beyond the block read its word 0, and
+// a pack in mode 0 has a block too, which nothing reads), so it is one more
+// load of the staging batch and the backend still counts what is in flight;
+// it is issued with the tile's own loads and stored to LDS with them, in
+// front of the staging barrier.
+HF_HD constexpr size_t air_table_lds_offset(int NC) {
+  return ((size_t)LEAN_TILE_FIELDS_SG * NC * sizeof(real) + 7) & ~(size_t)7;
+}
+constexpr size_t AIR_TABLE_LDS_BYTES = sizeof(AirTable);
+__device__ __forceinline__ unsigned long long air_table_issue(const SpeciesProps* sp) {
+  const unsigned t = threadIdx.x < (unsigned)AIR_TABLE_WORDS ? threadIdx.x : 0u;
+  return reinterpret_cast<const unsigned long long*>(air_table_of(sp))[t];
+}
+__device__ __forceinline__ void air_table_write(AirTable* tab, unsigned long long w) {
+  if (threadIdx.x < (unsigned)AIR_TABLE_WORDS) reinterpret_cast<unsigned long long*>(tab)[threadIdx.x] = w;
+}
+
 // Workgroup 0's once-per-step updates of the scalars, after P.dt is known
 // (MIRROR: the host mirror's part, host_mirror_head).
 template <bool MIRROR, bool FX>
@@ -220,6 +239,15 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
   }
   // staged from the state arrays alone (not an edge tile of a fused exchange)
   const bool plain = !FX || seq_prev == 0 || (X.skip & 4) || (i0 - 1 > P.i0 - 1 && i0 + T.TI < P.i1);
+  // (single gas: the AirTable travels with whichever staging follows)
+  static_assert(NT >= AIR_TABLE_WORDS, "one AirTable word per thread");
+  AirTable* tab = nullptr;
+  unsigned long long tabw = 0;
+  if constexpr (SG) {
+    extern __shared__ double lds8[];   // (the same LDS; 8-byte aligned in the FP32 build too)
+    tab = reinterpret_cast<AirTable*>(reinterpret_cast<char*>(lds8) + air_table_lds_offset(T.NC));
+    tabw = air_table_issue(P.species);
+  }
   if (SG && plain) {
     // Ordered so that a wave's independent loads overlap: the dt word and
     // the own cells' CT / lb are in flight; the whole staging is issued next,
@@ -284,6 +312,7 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
       lds[(FU + 2) * T.NC + c] = L.Pin[g];
     }
   }
+  if constexpr (SG) air_table_write(tab, tabw);
   __syncthreads();
   if (SG && b == 0) lean_tile_wg0_head<OUT && !RES && !FX, FX>(P, sc, slot, slot_next, X, seq_prev);
   // (raising the wave priority here for the compute phase, s_setprio 2,
@@ -298,6 +327,10 @@ __device__ __forceinline__ void lean_tile_body(StepParams& P, const LeanSoA& L, 
   for (int q = 0; q < CPT; q++) {
     if (mine[q]) {
       TileIO<SG> io(L, (long)i[q] * P.ny + j[q], lds, T.NC, T.W, c[q]);
+      if constexpr (SG) {
+        io.tab = tab;
+        io.table = T.table;
+      }
       dtl = fmin(dtl, lean_cell<RES, OUT>(P, L, io, own[q], i[q], j[q], r, &neg));
       if (FX) {
         const bool pl = (X.sides & 1) && i[q] == P.i0, pr = (X.sides & 2) && i[q] == P.i1 - 1;

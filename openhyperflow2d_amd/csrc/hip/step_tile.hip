@@ -102,6 +102,56 @@ int lean_tile_stage_kmax(int nt, int cpt) {
   return (nt == BLOCK || nt == 128 || nt == 64) && (cpt == 1 || cpt == 2) ? lean_stage_kmax(nt, cpt) : 0;
 }
 
+// Cp_air(xv[t]) as the single-gas tile kernels evaluate it: the pack's AirTable
+// through air_table_issue / air_table_write into LDS, then air_table_eval
+// (mode 1) or table_eval on the pack (mode 0).  One workgroup of one wave.
+__global__ __launch_bounds__(WAVE) void hf2d_air_table_probe(const SpeciesProps* sp, const real* xv, real* out, int n,
+                                                             int table) {
+  extern __shared__ double lds8[];
+  AirTable* tab = reinterpret_cast<AirTable*>(lds8);
+  air_table_write(tab, air_table_issue(sp));
+  __syncthreads();
+  const int t = (int)threadIdx.x;
+  if (t < n) out[t] = table ? air_table_eval(*tab, xv[t]) : table_eval(sp->Cp[H_AIR], xv[t]);
+}
+
+std::pair<std::vector<double>, int> air_table_probe(const std::vector<double>& x, const std::vector<double>& y,
+                                                    const std::vector<double>& xv) {
+  if (x.size() != y.size() || x.size() > (size_t)MAX_TABLE_PTS) throw std::runtime_error("air_table_probe: table size");
+  if (xv.size() > (size_t)WAVE) throw std::runtime_error("air_table_probe: at most 64 values per call");
+  SpeciesDev sd;
+  sd.sp.R[H_AIR] = 287.0;
+  TableData& t = sd.sp.Cp[H_AIR];
+  t.n = (int)x.size();
+  for (int k = 0; k < MAX_TABLE_PTS; k++) {
+    t.x[k] = k < t.n ? x[k] : 0.0;
+    t.y[k] = k < t.n ? y[k] : 0.0;
+  }
+  sd.air = air_table_build(sd.sp);
+  const int n = (int)xv.size();
+  std::vector<real> hx(xv.begin(), xv.end()), ho(WAVE, (real)0);
+  hx.resize(WAVE, (real)0);
+  SpeciesDev* dsd = nullptr;
+  real* dx = nullptr;
+  HIP_CHECK(hipMalloc((void**)&dsd, sizeof(SpeciesDev)));
+  if (hipMalloc((void**)&dx, 2 * WAVE * sizeof(real)) != hipSuccess) {
+    (void)hipFree(dsd);
+    throw std::runtime_error("air_table_probe: hipMalloc");
+  }
+  hipError_t e = hipMemcpy(dsd, &sd, sizeof(SpeciesDev), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dx, hx.data(), WAVE * sizeof(real), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(hf2d_air_table_probe, dim3(1), dim3(WAVE), AIR_TABLE_LDS_BYTES, 0, &dsd->sp, dx, dx + WAVE, n,
+                       sd.air.mode);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(ho.data(), dx + WAVE, WAVE * sizeof(real), hipMemcpyDeviceToHost);
+  (void)hipFree(dx);
+  (void)hipFree(dsd);
+  if (e != hipSuccess) throw std::runtime_error(std::string("air_table_probe: ") + hipGetErrorString(e));
+  return {std::vector<double>(ho.begin(), ho.begin() + n), sd.air.mode};
+}
+
 using LeanEulerK =void (*)(StepParams, LeanSoA, long, long, DevScalars*, int, int, int, ResidualPack*);
 // [residual][first lean step: from the generic arrays]
 static const LeanEulerK kLeanEuler[2][2] = {{hf2d_lean_euler<false, false>, hf2d_lean_euler<false, true>},
@@ -145,7 +195,9 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
   LeanTile T = lean_tile_geom(P.i1 - P.i0, P.ny, nt, lean_tj, cpt);
   T.stage = sg ? tile_stage_k(T, nt, cpt) : 0;
   const unsigned ntile = (unsigned)(T.nbi * T.nbj);
-  size_t shmem = (size_t)lean_tile_fields(sg) * T.NC * sizeof(real);
+  T.table = sg ? air_table_mode : 0;
+  // (single gas: the AirTable behind the fields, in either mode)
+  size_t shmem = sg ? air_table_lds_offset(T.NC) + AIR_TABLE_LDS_BYTES : (size_t)lean_tile_fields(sg) * T.NC * sizeof(real);
   if (lean_wgcu > 0)   // cap the resident workgroups per CU through the LDS request (160 KB per CU)
     shmem = std::max(shmem, (size_t)((LDS_PER_CU / lean_wgcu - 1024) & ~255));
   // an armed recorder needs T of every step, which the plain variant does
@@ -176,6 +228,7 @@ DeviceSolver::StepDone DeviceSolver::step_tile(StepCtx& c) {
   lean_tile_last.nbi = T.nbi;
   lean_tile_last.nbj = T.nbj;
   lean_tile_last.stage = T.stage;
+  lean_tile_last.table = T.table;
   // (the stagger block is compiled into the single-gas two-cell 256-thread plain kernel only)
   lean_tile_last.stagger = HF2D_TILE_STAGGER && sg && cpt == 2 && !fx_step && nt == BLOCK ? P.stagger : 0;
   lean_tile_last.fx = fx_step ? 1 : 0;
