@@ -44,7 +44,7 @@ GPU paths (test_gpu_model_families.py asserts which kernels ran):
              N-S tiles, through lns_materialize() at the cycle boundary and
              the lean re-entry after it.
 
-Left out: wall_law (stops with Tg < 0 at iteration 3 by design);
+Left out: wall_law (stops with Tg < 0 at iteration 3 by design: test_gpu_failure_paths.py);
 restart_from_hf2d (resumes from a checkpoint, no cold start to perturb);
 wedge_keps_wallheat, step_euler, oblique_shock, wedge15_200x40_euler and
 wedge15_200x60_ns_keps (large, and test_gpu_kernels.py already marches them).
